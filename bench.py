@@ -16,9 +16,18 @@ from rank 0 with ncclBroadcast (RCCL over xGMI, ctypes, p265_amd/rccl.py) once, 
 timed region; barriers and the MAX over ranks go over the socket control plane.  Rank 0
 prints ONE JSON line.
 
-    python bench.py                       # N=1, defaults finish in ~1-2 minutes
+    python bench.py                       # N=1: set up, warm up, time the steps, print the line
+    python bench.py --full                # + every other leg below; finishes in ~1-2 minutes
     python bench.py --gpus 8              # launches 8 rank processes itself (one per device)
     python -m torch.distributed.run --nproc-per-node 8 bench.py --gpus 8
+
+A plain run does only what `value` / `ms_per_step` need.  --full adds, after the timed steps, everything
+else the line can carry: the per-phase pass and roofline, the output check against the C oracle
+(`verified`, exit 3 on a mismatch), the stream / issue ceilings, the CPU baselines, the PCIe-fed and
+bitstream end-to-end legs and C5's unit latency (--no-cpu-baseline / --no-e2e / --no-pcie / --no-verify
+drop single legs of it).  --dump-outputs DIR writes the planes the last timed step produced (a fixed
+sample of its pictures) as DIR/<name>.npy, float32: the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 Without a launcher (WORLD_SIZE unset) and N > 1, this process only spawns the N rank processes
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torch.distributed.run sets them) before anything
@@ -169,9 +178,15 @@ def parse(argv=None):
                     help="resident batches run round-robin on this many HIP streams (p265r_set_pipeline; default "
                          "2 -- one batch's residual / prep / SAO phases beside the other's intra phase; c5 with "
                          "--c5-batch-units 0: 16 -- an 8-unit batch fills 16 CUs, so 16 whole batches run side by side)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: phase pass + roofline, output check against "
+                         "the C oracle, stream / issue ceilings, CPU baselines, PCIe and end-to-end legs, c5 unit latency")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output planes of the last timed step (a fixed sample of its pictures, at most "
+                         "64 MB) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the bitstream -> planes end-to-end leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the bitstream -> planes end-to-end leg")
     ap.add_argument("--deblocking", action="store_true",
                     help="deblocking on in every slice (real-stream config; SURVEY §8(d) defines the bench without it)")
     ap.add_argument("--experiment", action="store_true",
@@ -179,11 +194,11 @@ def parse(argv=None):
     ap.add_argument("--no-rccl", action="store_true",
                     help="N > 1: control plane only, no RCCL communicator (ranks sharing one device: two RCCL "
                          "ranks cannot); the params then travel over the control plane")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run output check (not a headline run)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the post-run output check")
     ap.add_argument("--device-map", default=None,
                     help="N > 1: comma-separated HIP device of each local rank (default: local rank i on device i); "
                          "ranks sharing a device need --no-rccl (tests: --gpus 2 --device-map 0,0 --no-rccl)")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive back-end leg")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive back-end leg")
     ap.add_argument("--bit-depth", type=int, default=8, choices=(8, 9, 10, 11, 12),
                     help="c3: BitDepth of the synthetic pictures (9 / 10: the Main 10 path -- uint16 planes, per-diagonal "
                          "intra kernel, loopfilter16.h; not the headline)")
@@ -616,6 +631,47 @@ def c5_unit_latency(ctx, step_pics, runs):
             "note": "one step's %d tile units of this rank as one batch, alone, %d runs" % (len(step_pics), n)}
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # float32 bytes of the dumped planes per rank (--dump-outputs)
+
+
+def pictures_to_dump(plane_samples, budget=DUMP_BUDGET_BYTES):
+    """Indices of a batch's pictures whose planes --dump-outputs writes: all of them when they fit the
+    budget as float32, else the first, the last and a seeded draw of the others (the same for every
+    run of the same workload).  ``plane_samples``: samples per picture (three planes), per picture."""
+    n = len(plane_samples)
+    if 4 * sum(plane_samples) <= budget:
+        return list(range(n))
+    keep = max(1, int(budget // (4 * max(plane_samples))))
+    idx = [0, n - 1][:keep]
+    rest = np.random.default_rng(265).permutation(np.arange(1, n - 1))
+    return sorted(idx + [int(i) for i in rest[:keep - len(idx)]])
+
+
+def dump_outputs(path, ctxs, slot, rank, world):
+    """--dump-outputs: the output planes of the last timed step -- batch ``slot`` of every context, what
+    ReconContext.download() hands a caller after that run -- for pictures_to_dump()'s sample, as
+    <path>/[rank<r>_]ctx<c>_pic<i>_<y|cb|cr>.npy in float32 (8- to 12-bit samples: exact).
+    -> the line's "dumped_outputs" object."""
+    os.makedirs(path, exist_ok=True)
+    files = nbytes = 0
+    chosen = []
+    for ci, (ctx, batches) in enumerate(ctxs):
+        b = batches[slot]
+        idx = pictures_to_dump([int(p.meta["samples"]) for p in b.pics], DUMP_BUDGET_BYTES // len(ctxs))
+        outs = ctx.download(b, only=idx)
+        for i in idx:
+            for name, plane in zip(("y", "cb", "cr"), outs[i]):
+                f = "%sctx%d_pic%05d_%s.npy" % ("rank%d_" % rank if world > 1 else "", ci, i, name)
+                arr = np.ascontiguousarray(plane, np.float32)
+                np.save(os.path.join(path, f), arr)
+                files += 1
+                nbytes += arr.nbytes
+        chosen.append(idx)
+    return {"dir": path, "files": files, "bytes": nbytes, "batch_slot": slot, "pictures": chosen,
+            "how": "planes of the last timed step's batch as ReconContext.download() returns them, float32; "
+                   "a fixed sample of the batch's pictures (first, last, seeded draw)"}
+
+
 class Refused(SystemExit):
     """A command-line / environment combination bench.py will not run (exit 2, message on stderr)."""
 
@@ -718,6 +774,8 @@ def main(argv=None):
         a.pipeline = 16 if c5_latency else 2
     if a.steps is None:
         a.steps = 64 if c5_latency else (20 if a.workload == "c5" else 30)
+    if a.steps < 1 or a.warmup < 0:
+        raise Refused("--steps %d --warmup %d (at least one timed step, no negative warm-up)" % (a.steps, a.warmup))
     # one hardware queue per stream (the lanes + the upload stream): HIP's default 4 would put two C5
     # lanes behind each other (c5, 8 lanes: 3.0 M CTU/s at 4 queues, 8.4 M at 12; 16 lanes at 20 queues:
     # 16.4 M, every CU holding one unit's workgroup; c3 measured best
@@ -740,9 +798,9 @@ def main(argv=None):
     from p265_amd import dist, hip, recon
 
     host = host_info()
-    # pure-Python CPU baseline first, in a child process, before this process touches the GPU
+    # --full: pure-Python CPU baseline first, in a child process, before this process touches the GPU
     py_base = None
-    if world_env == 1 and not a.no_cpu_baseline and a.workload == "c3" and a.bit_depth == 8:
+    if a.full and world_env == 1 and not a.no_cpu_baseline and a.workload == "c3" and a.bit_depth == 8:
         py_base = cpu_baseline_python(host["cpu_share"])
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if local_rank >= len(dmap):
@@ -796,6 +854,95 @@ def main(argv=None):
         for k, v in ctx.describe()["row_launches"].items():
             if v - b0[k]:
                 builds_timed[k] = builds_timed.get(k, 0) + v - b0[k]
+    dumped = None
+    if a.dump_outputs:                     # before any later pass runs the batches again
+        dumped = dump_outputs(a.dump_outputs, ctxs, (a.steps - 1) % a.pipeline, rank, world)
+    knobs = ctxs[0][0].describe()
+
+    if a.workload == "c3":
+        total_ctus = world * n_ctu * a.steps
+    elif a.c5_world:                       # this GPU's share of a simulated c5_world-rank job
+        total_ctus = n_ctu * a.steps
+    else:                                  # every tile unit of the batch's steps, over all ranks
+        total_ctus = cfg["ctus_all_units"] * cfg["steps_per_batch"] * a.steps
+    value = total_ctus / elapsed
+    cfg.update(batch_pipeline=a.pipeline, library=knobs)
+    out = {
+        "metric": METRIC,
+        "value": round(value, 1), "unit": "CTU/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak" if a.workload == "c3" else "strong",
+        "vs_baseline": None, "dtype": "%s samples / int16 coefficients (integer)" % ("u8" if a.bit_depth == 8 else "u16"),
+        "data": "synthetic: seeded all-intra records with sanity.bin statistics (p265_amd/synth.py)",
+        "config": cfg, "full": bool(a.full), "setup_s": round(gen_s, 1),
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if a.full:
+        figs, launches_per_step, avg_launch_ms, jobs = phase_figures(a, ctxs, pics, elapsed, builds_timed)
+        out.update(figs)
+        if a.workload == "c5":
+            out["unit_latency_ms"] = c5_unit_latency(ctxs[0][0], cpu_sample, a.steps)
+    if a.c5_world:
+        out["per_gpu_of_world"] = a.c5_world
+        out["value_note"] = ("this GPU's rate for rank 0's share of a %d-rank job (%d of the %d tile units of every "
+                             "step); the whole job's rate is %d x this when every rank holds as many units"
+                             % (a.c5_world, cfg["units_per_rank_step"], cfg["units_per_step"], a.c5_world))
+    if exp:
+        out["experiment_env"] = exp
+    if world > 1:
+        out["collectives"] = {"kind": ("control plane only (--no-rccl)" if a.no_rccl else
+                                       "ncclBroadcast of the 32-B params (RCCL); barriers + MAX over the control plane"),
+                              "rccl_ranks": rccl_ranks, "devices": dist.allgather_json(local),
+                              "launcher": "torch.distributed.run or bench.py's own (--gpus N, WORLD_SIZE unset)"}
+    if a.full and not a.no_verify:
+        wants = oracle_digests(groups, host["cpu_share"])
+        v = verify(ctxs, groups, a, wants, ran)
+        cp = checked_pass(ctxs, groups, a, wants, a.steps)
+        v["every_run"] = cp
+        v["ok"] = v["ok"] and cp["ok"]
+        # every rank checks its own batches; the job is ok only if all are
+        v["ranks_failed"] = int(dist.max_over_ranks(0.0 if v["ok"] else 1.0)) if world > 1 else int(not v["ok"])
+        v["ok"] = v["ok"] and v["ranks_failed"] == 0
+        out["verified"] = v
+    if a.full and rank == 0:
+        sc = stream_ceiling(local)
+        out["roofline"]["achievable"] = sc
+        ceil = sc.get("copy_gbs") or sc["memcpy_d2d_gbs"]
+        out["phase_gbs"]["vs_achievable_copy"] = {k: round(v / ceil, 3) for k, v in out["phase_gbs"].items()
+                                                  if isinstance(v, float) and k != "whole_path_algorithmic"}
+        if a.workload == "c3" and launches_per_step == 1 and a.bit_depth == 8:
+            out["roofline"]["issue"] = issue_ceiling(local, avg_launch_ms, jobs,
+                                                     int(knobs.get("num_cus", 256)), out["issue_rates"])
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if py_base is not None:
+            py_base.update(host_cores_total=host["host_cores_total"], cpu_model=host["cpu_model"])
+            out["cpu_baseline"] = py_base
+        cb = cpu_baseline(cpu_params, cpu_sample, a.cpu_baseline_seconds, host["cpu_share"], cpu_what)
+        cb.update(host_cores_total=host["host_cores_total"], cpu_model=host["cpu_model"])
+        out["cpu_baseline_c" if py_base is not None else "cpu_baseline"] = cb
+    out["host"] = host
+    for ctx, batches in ctxs:
+        for b in batches:
+            b.free()
+        ctx.close()
+    if a.full and rank == 0 and world == 1 and not a.no_pcie and a.workload == "c3":
+        out["pcie"] = pcie_leg(groups[0][0], groups[0][1], local)
+    if a.full and rank == 0 and world == 1 and not a.no_e2e and a.workload == "c3" and a.bit_depth == 8:
+        out["end_to_end"] = end_to_end(local, threads=min(16, host["cpu_share"]))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    dist.finalize()
+    rc = exit_code(out)
+    if rc:
+        sys.stderr.write("bench.py: output check FAILED: %s\n" % json.dumps(out.get("verified")))
+    return rc
+
+
+def phase_figures(a, ctxs, pics, elapsed, builds_timed):
+    """--full: the phase breakdown and the roofline block of the line, from passes of their own after the
+    timed steps.  -> (the line's keys, intra launches per step, the intra kernel's isolated ms per launch,
+    intra jobs per launch)."""
     # phase breakdown + roofline: the same steps on ONE batch per context (one stream, no
     # overlap, contexts one after another), HIP events around each phase, so every kernel's
     # duration is its own
@@ -809,7 +956,6 @@ def main(argv=None):
         t = ctx.timings_total()
         assert t["runs"] == a.steps
         acc = t if acc is None else {k: acc[k] + t[k] for k in acc}
-    knobs = ctxs[0][0].describe()
     jl, jch = ctxs[0][0].job_count(ctxs[0][1][0])
     # the pipelined steps' row kernel after the first is the W = 8 build (beside the other lane's phases):
     # the same batch alone through that build, so the line carries both builds' isolated launch times
@@ -825,14 +971,6 @@ def main(argv=None):
         ctx0.set_row_waves(0)
         t8 = ctx0.timings_total()
         w8 = t8["intra_ms"] / max(1, t8["intra_launches"])
-
-    if a.workload == "c3":
-        total_ctus = world * n_ctu * a.steps
-    elif a.c5_world:                       # this GPU's share of a simulated c5_world-rank job
-        total_ctus = n_ctu * a.steps
-    else:                                  # every tile unit of the batch's steps, over all ranks
-        total_ctus = cfg["ctus_all_units"] * cfg["steps_per_batch"] * a.steps
-    value = total_ctus / elapsed
     tot_b, intra_b, res_b, sao_b = algorithmic_bytes(pics, 1 if a.bit_depth == 8 else 2)
     launches_per_step = acc["intra_launches"] / a.steps
     avg_launch_ms = acc["intra_ms"] / max(1, acc["intra_launches"])
@@ -842,15 +980,7 @@ def main(argv=None):
         traffic, prof_tag = measured_traffic(a.workload, "intra_rows_kernel", len(pics), avg_launch_ms)
     else:                                  # the 16-bit path's kernels have no committed PMC profile
         traffic, prof_tag = None, "not profiled (Main 10 path)"
-    cfg.update(batch_pipeline=a.pipeline, library=knobs)
     out = {
-        "metric": METRIC,
-        "value": round(value, 1), "unit": "CTU/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": "weak" if a.workload == "c3" else "strong",
-        "vs_baseline": None, "dtype": "%s samples / int16 coefficients (integer)" % ("u8" if a.bit_depth == 8 else "u16"),
-        "data": "synthetic: seeded all-intra records with sanity.bin statistics (p265_amd/synth.py)",
-        "config": cfg,
         "roofline": {"bound": "hbm", "kernel": "intra_rows_kernel" if a.bit_depth == 8 else
                      ("intra_rows_kernel<..., uint16_t>" if a.bit_depth <= 10 else
                       "intra_rows_kernel<..., int16_t>"), "achieved": round(achieved, 2),
@@ -875,7 +1005,6 @@ def main(argv=None):
         "phase_gbs": {"residual": round(res_b / (acc["residual_ms"] / a.steps * 1e-3) / 1e9, 1),
                       "sao": round(sao_b / (acc["sao_ms"] / a.steps * 1e-3) / 1e9, 1) if acc["sao_ms"] else None,
                       "whole_path_algorithmic": round(tot_b / (elapsed / a.steps) / 1e9, 2)},
-        "setup_s": round(gen_s, 1),
     }
     builds = {"timed_steps_launches": builds_timed,
               "w12_alone": {"avg_launch_ms": round(avg_launch_ms, 4), "frac": round(achieved / HBM_PEAK_GBS, 4)}}
@@ -883,62 +1012,7 @@ def main(argv=None):
         builds["w8_alone"] = {"avg_launch_ms": round(w8, 4),
                               "frac": round(bytes_per_launch / (w8 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
     out["roofline"]["builds"] = builds
-    if a.workload == "c5":
-        out["unit_latency_ms"] = c5_unit_latency(ctxs[0][0], cpu_sample, a.steps)
-        if a.c5_world:
-            out["per_gpu_of_world"] = a.c5_world
-            out["value_note"] = ("this GPU's rate for rank 0's share of a %d-rank job (%d of the %d tile units of every "
-                                 "step); the whole job's rate is %d x this when every rank holds as many units"
-                                 % (a.c5_world, cfg["units_per_rank_step"], cfg["units_per_step"], a.c5_world))
-    if exp:
-        out["experiment_env"] = exp
-    if world > 1:
-        out["collectives"] = {"kind": ("control plane only (--no-rccl)" if a.no_rccl else
-                                       "ncclBroadcast of the 32-B params (RCCL); barriers + MAX over the control plane"),
-                              "rccl_ranks": rccl_ranks, "devices": dist.allgather_json(local),
-                              "launcher": "torch.distributed.run or bench.py's own (--gpus N, WORLD_SIZE unset)"}
-    if not a.no_verify:
-        wants = oracle_digests(groups, host["cpu_share"])
-        v = verify(ctxs, groups, a, wants, ran)
-        cp = checked_pass(ctxs, groups, a, wants, a.steps)
-        v["every_run"] = cp
-        v["ok"] = v["ok"] and cp["ok"]
-        # every rank checks its own batches; the job is ok only if all are
-        v["ranks_failed"] = int(dist.max_over_ranks(0.0 if v["ok"] else 1.0)) if world > 1 else int(not v["ok"])
-        v["ok"] = v["ok"] and v["ranks_failed"] == 0
-        out["verified"] = v
-    if rank == 0:
-        sc = stream_ceiling(local)
-        out["roofline"]["achievable"] = sc
-        ceil = sc.get("copy_gbs") or sc["memcpy_d2d_gbs"]
-        out["phase_gbs"]["vs_achievable_copy"] = {k: round(v / ceil, 3) for k, v in out["phase_gbs"].items()
-                                                  if isinstance(v, float) and k != "whole_path_algorithmic"}
-        if a.workload == "c3" and launches_per_step == 1 and a.bit_depth == 8:
-            out["roofline"]["issue"] = issue_ceiling(local, avg_launch_ms, jl + jch,
-                                                     int(knobs.get("num_cus", 256)), out["issue_rates"])
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        if py_base is not None:
-            py_base.update(host_cores_total=host["host_cores_total"], cpu_model=host["cpu_model"])
-            out["cpu_baseline"] = py_base
-        cb = cpu_baseline(cpu_params, cpu_sample, a.cpu_baseline_seconds, host["cpu_share"], cpu_what)
-        cb.update(host_cores_total=host["host_cores_total"], cpu_model=host["cpu_model"])
-        out["cpu_baseline_c" if py_base is not None else "cpu_baseline"] = cb
-    out["host"] = host
-    for ctx, batches in ctxs:
-        for b in batches:
-            b.free()
-        ctx.close()
-    if rank == 0 and world == 1 and not a.no_pcie and a.workload == "c3":
-        out["pcie"] = pcie_leg(groups[0][0], groups[0][1], local)
-    if rank == 0 and world == 1 and not a.no_e2e and a.workload == "c3" and a.bit_depth == 8:
-        out["end_to_end"] = end_to_end(local, threads=min(16, host["cpu_share"]))
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    dist.finalize()
-    rc = exit_code(out)
-    if rc:
-        sys.stderr.write("bench.py: output check FAILED: %s\n" % json.dumps(out.get("verified")))
-    return rc
+    return out, launches_per_step, avg_launch_ms, jl + jch
 
 
 if __name__ == "__main__":

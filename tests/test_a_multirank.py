@@ -100,7 +100,7 @@ def test_bench_two_ranks_on_one_device():
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), P265_CTRL_PORT=str(ctrl))
         env = {k: v for k, v in env.items() if not k.startswith("P265R_")}
         procs.append(subprocess.Popen([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                                       "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
+                                       "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e",
                                        "--no-rccl"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = []
@@ -158,7 +158,8 @@ def test_bench_self_launched_two_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
            and not k.startswith("P265R_")}
     p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device-map", "0,0",
-                        "--no-rccl", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-pcie"],
+                        "--no-rccl", "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e",
+                        "--no-pcie"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

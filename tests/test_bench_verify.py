@@ -57,6 +57,27 @@ def test_pictures_to_check_covers_both_ends():
     assert b.pictures_to_check(8, 8) == list(range(8))
 
 
+def test_pictures_to_dump_is_a_fixed_sample_within_the_budget():
+    """--dump-outputs: every picture when the batch fits, else the first, the last and a seeded draw --
+    the same indices on every call, at most the budget in float32."""
+    b = _bench()
+    one = 1920 * 1080 * 3 // 2
+    assert b.pictures_to_dump([one] * 3) == [0, 1, 2]
+    idx = b.pictures_to_dump([one] * 512)
+    assert idx == b.pictures_to_dump([one] * 512) and idx == sorted(set(idx))
+    assert idx[0] == 0 and idx[-1] == 511 and len(idx) == 4
+    assert 4 * one * len(idx) <= b.DUMP_BUDGET_BYTES <= 64 << 20
+    assert b.pictures_to_dump([one] * 2, budget=4 * one) == [0]
+
+
+def test_plain_and_full_runs_parse():
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = b.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+
+
 def test_verify_accepts_the_oracle_digests_and_flags_a_corrupted_picture():
     b = _bench()
     params = R.make_params(pic_width=128, pic_height=64)

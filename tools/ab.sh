@@ -28,7 +28,7 @@ for rep in $(seq ${REPS:-2}); do
     exp=""
     [[ "$envs $libenv" == *P265R_* ]] && exp="--experiment"
     log=$ROOT/gpurun_out/ab/$name.$rep.log
-    (cd $dir && env $envs $libenv timeout -k 10 300 python bench.py $exp --no-cpu-baseline --no-e2e \
+    (cd $dir && env $envs $libenv timeout -k 10 300 python bench.py --full $exp --no-cpu-baseline --no-e2e \
         ${args:---steps 20 --warmup 5}) > $log 2>&1 || { echo "[$rep] $name FAILED"; tail -5 $log; continue; }
     python3 - "$log" "$rep" "$name" <<'PY'
 import json, sys

@@ -2,7 +2,7 @@
 # One GPU call: the whole -m gpu suite (verbose, per-test timeout), then optional bench lines
 # (BENCHES: ';'-separated bench.py argument lists) and an interleaved A/B of the bench over the
 # configurations in CFGS (tools/ab.sh).
-#   BENCHES="--workload c5 --steps 10;--steps 20 --warmup 5" CFGS="base|-||;v|variant||" REPS=3 bash tools/gpu_round.sh
+#   BENCHES="--full --workload c5 --steps 10;--full --steps 20 --warmup 5" CFGS="base|-||;v|variant||" REPS=3 bash tools/gpu_round.sh
 set -e
 mkdir -p gpurun_out
 if [ -z "$NO_TESTS" ]; then

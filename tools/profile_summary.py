@@ -65,7 +65,7 @@ def main(src, tag):
     iso = isolated_avg(os.path.join(src, "kt", "kt_kernel_trace.csv"))
     out = {}
     cmd = os.path.join(src, "cmd.txt")
-    what = open(cmd).read().strip() if os.path.exists(cmd) else "python bench.py --frames 512 --steps 3 --warmup 1 --unique 2"
+    what = open(cmd).read().strip() if os.path.exists(cmd) else "python bench.py --full --frames 512 --steps 3 --warmup 1 --unique 2"
     if os.path.exists(os.path.join(src, "bench.json")):
         shutil.copy(os.path.join(src, "bench.json"), os.path.join(dst, "bench.json"))
     lines = ["# rocprofv3 summary `%s` (`%s`)" % (tag, what), "",
