@@ -22,9 +22,12 @@ Parity status: the front-end records that feed this oracle are pinned by the
 reference's 95 golden trace files (tests/golden/gen_sanity_fixture.py).  The
 planar, DC, horizontal-family angular, modes 18/26/34, neighbour filtering and
 scaling functions are pinned against outputs of the reference's own functions
-(tests/golden/gen_component_fixture.py).  The inverse transform, the vertical
-angular modes the reference gets wrong, substitution when the bottom-left sample
-is present, deblocking and SAO filtering have no reference output to pin against: for those
+(tests/golden/gen_component_fixture.py).  The vertical angular modes the reference
+gets wrong and luma mode 10 are pinned through its correct horizontal branch by the
+transposition symmetry of 8.4.4.2.6, and whole substitution -> filtering -> prediction
+chains by its decode_neighbor (--pins; tests/test_planted.py).  The inverse transform,
+substitution when the bottom-left sample is present and another is missing,
+deblocking and SAO filtering have no reference output to pin against: for those
 parity is UNPINNED by the reference and rests on spec restatement + known-answer
 tests (tests/test_oracle_kat.py).
 
@@ -445,6 +448,11 @@ def reconstruct_picture(params, pic):
     return planes
 
 
+def clip_reconstruction(pred, res, bit_depth):
+    """8.6.7 picture construction: Clip1(predSamples + resSamples) (reconstruction.py:23-25)."""
+    return np.clip(np.asarray(pred, np.int64) + np.asarray(res, np.int64), 0, (1 << bit_depth) - 1)
+
+
 def _recon_tb(geo, planes, t, coef, bd, strong, sf=None):
     c_idx, log2 = int(t["c_idx"]), int(t["log2_size"])
     n = 1 << log2
@@ -472,7 +480,7 @@ def _recon_tb(geo, planes, t, coef, bd, strong, sf=None):
         p = filter_refs(p, n, mode, c_idx, strong, bd[c_idx])
         pred = predict(p, n, mode, c_idx, bd[c_idx])
     h, w = plane.shape
-    rec = np.clip(pred + res, 0, (1 << bd[c_idx]) - 1)     # reconstruction.py:23-25
+    rec = clip_reconstruction(pred, res, bd[c_idx])
     plane[y0:min(y0 + n, h), x0:min(x0 + n, w)] = rec[: h - y0, : w - x0]
 
 

@@ -27,6 +27,11 @@ Usage:  PYTHONDONTWRITEBYTECODE=1 python3 -B tests/golden/gen_component_fixture.
 BitDepthY = BitDepthC = 10 and QpBdOffset = 12 (scaling.py:14-26 bdShift and qP, reconstruction.py:25
 and utils.py:11-15 clip, intra.py:241 substitution default, intra.py:280-281 strong-filter threshold,
 intra.py:160 edge-filter clip), samples 0..1023 and QpY -12..51.  The 8-bit run is unchanged.
+
+--pins [--bit-depth N] writes ref_pins*.npz / ref_chain*.npz (main_pins): the vertical angular family and
+luma mode 10 from the reference's correct branches by transposition, and whole neighbour-to-prediction
+chains for the availability patterns its substitution gets right.  It draws from a generator of its own
+and checks that ref_components*.npz still has its recorded SHA-256.
 """
 import contextlib
 import hashlib
@@ -267,13 +272,174 @@ def main_scaling():
     print(json.dumps(meta, indent=1))
 
 
+# availability of (bottom-left, left, corner, top, top-right) the reference substitutes correctly
+# (intra.py:243 handles only a missing p[-1][2N-1]); tests/planted.py has a placement for each
+CHAIN_PATTERNS = [("interior", (1, 1, 1, 1, 1)), ("bl_missing", (0, 1, 1, 1, 1)), ("both_missing", (0, 1, 1, 1, 0)),
+                  ("left_edge", (0, 0, 0, 1, 1)), ("origin", (0, 0, 0, 0, 0))]
+PIN_STYLES = ("ramp", "random", "flat", "extremes")
+
+
+def _pin_values(rng, style, m, bd):
+    sh, mx = bd - 8, (1 << bd) - 1
+    if style == "ramp":
+        return np.clip(rng.integers(0, 200 << sh) + np.cumsum(rng.integers(-3 << sh, (3 << sh) + 1, m)), 0, mx)
+    if style == "random":
+        return rng.integers(0, mx + 1, m)
+    if style == "flat":
+        return np.clip((128 << sh) + rng.integers(-2, 3, m), 0, mx)
+    return rng.integers(0, 2, m) * mx                                  # extremes: every value 0 or max
+
+
+def _plain(nb, n):
+    """The reference's nested neighbour dict as plain dicts (a stray read then raises instead of growing
+    an md_dict), [x][y]."""
+    dx, dy = O.ref_positions(n)
+    d = {}
+    for a, b in zip(dx, dy):
+        d.setdefault(int(a), {})[int(b)] = int(nb[int(a)][int(b)])
+    return d
+
+
+def _transposed(nb):
+    t = {}
+    for x, col in nb.items():
+        for y, v in col.items():
+            t.setdefault(y, {})[x] = v
+    return t
+
+
+def _ref_predict(intra, sps, nb, n, mode, c_idx):
+    """pred[y][x] of the reference's prediction functions on the plain neighbour dict ``nb`` [x][y].  The
+    vertical family with iFact != 0 (19..25, 27..33: intra.py:155-158 swaps the branches), mode 34 (reads
+    past its ref dict) and luma mode 10 below 32x32 (intra.py:184 calls an undefined clip) go through the
+    reference's correct branch by the transposition symmetry of 8.4.4.2.6: mode 36 - m on the transposed
+    neighbours, its output read as [y][x]."""
+    log2 = int(np.log2(n))
+    cu = _NS(ctx=_NS(sps=sps))
+    by_transposition = 19 <= mode <= 25 or 27 <= mode <= 34 or (mode == 10 and c_idx == 0 and n < 32)
+    pu = intra.IntraPu(cu, c_idx, 36 - mode if by_transposition else mode, log2, 0, 0)
+    if by_transposition:
+        pu.decode_intra_angular(_transposed(nb), 0, 0, log2)
+        return np.array(pu.predicted_samples), True
+    if mode == 0:
+        pu.decode_intra_planar(nb, 0, 0, log2)
+    elif mode == 1:
+        pu.decode_intra_dc(nb, 0, 0, log2)
+    else:
+        pu.decode_intra_angular(nb, 0, 0, log2)
+    return np.array(pu.predicted_samples).T, False
+
+
+def main_pins(bd=8):
+    """--pins: the vectors that pin what main() leaves unpinned, written to ref_pins*.npz and ref_chain*.npz
+    (arrays ragged: values and outputs concatenated, sizes follow from *_n).
+
+    ref_pins   vert_*: modes 19..25 and 27..34, every size, luma and chroma, four value styles, from the
+               reference's horizontal branch by transposition; m10_*: luma mode 10 below 32x32 from its mode 26.
+    ref_chain  decode_neighbor (substitution + filtering, luma) on planted values and availability, then
+               the prediction function: every CHAIN_PATTERNS x size x mode.
+    The reference raises in no case (nothing is caught here)."""
+    mods = _refshim.install("/tmp/p265_component_fixture")
+    _refshim.silence(mods)
+    intra = mods["intra"]
+    tag = "" if bd == 8 else "_bd%d" % bd
+    old = json.load(open(os.path.join(HERE, "ref_components%s.json" % tag)))["npz_sha256"]
+    assert hashlib.sha256(open(os.path.join(HERE, "ref_components%s.npz" % tag), "rb").read()).hexdigest() == old
+    rng = np.random.default_rng([SEED, 2, bd])
+    dt = np.uint8 if bd == 8 else np.uint16
+    off = 6 * (bd - 8)
+    sps = _NS(bit_depth_y=bd, bit_depth_c=bd, strong_intra_smoothing_enabled_flag=1, qp_bd_offset_y=off,
+              qp_bd_offset_c=off, scaling_list_enabled_flag=0)
+
+    def nb_of(L, n):
+        return _plain(_md(L), n)
+
+    vert = dict(n=[], mode=[], c=[], L=[], out=[])
+    vmodes = list(range(19, 26)) + list(range(27, 35))
+    for rep in range(4):
+        for c_idx in (0, 1):
+            for mi, mode in enumerate(vmodes):
+                for ni, n in enumerate((4, 8, 16, 32)):
+                    L = _pin_values(rng, PIN_STYLES[(rep + mi + ni) % 4], 4 * n + 1, bd)
+                    out, tr = _ref_predict(intra, sps, nb_of(L, n), n, mode, c_idx)
+                    assert tr
+                    for k, v in zip(("n", "mode", "c", "L", "out"), (n, mode, c_idx, L, out.reshape(-1))):
+                        vert[k].append(v)
+    m10 = dict(n=[], L=[], out=[])
+    clips = 0
+    for rep in range(20):
+        for ni, n in enumerate((4, 8, 16)):
+            L = _pin_values(rng, PIN_STYLES[(rep + ni) % 4], 4 * n + 1, bd)
+            out, tr = _ref_predict(intra, sps, nb_of(L, n), n, 10, 0)
+            assert tr
+            raw = L[2 * n - 1] + ((L[2 * n + 1: 3 * n + 1] - L[2 * n]) >> 1)
+            clips += int(((raw < 0) | (raw > (1 << bd) - 1)).any())
+            for k, v in zip(("n", "L", "out"), (n, L, out.reshape(-1))):
+                m10[k].append(v)
+    assert clips >= 10, "the mode 10 edge-filter clip should fire in many vectors"
+
+    chain = dict(n=[], mode=[], pattern=[], vals=[], avail=[], out=[])
+    for pi, (_, pattern) in enumerate(CHAIN_PATTERNS):
+        for ni, n in enumerate((4, 8, 16, 32)):
+            for mode in range(35):
+                m = 4 * n + 1
+                avail = np.zeros(m, bool)
+                for seg, on in zip((slice(0, n), slice(n, 2 * n), slice(2 * n, 2 * n + 1),
+                                    slice(2 * n + 1, 3 * n + 1), slice(3 * n + 1, m)), pattern):
+                    avail[seg] = bool(on)
+                vals = _pin_values(rng, PIN_STYLES[(pi + ni + mode) % 4], m, bd)
+                dx, dy = O.ref_positions(n)
+                x0 = y0 = 64
+                lut = {(x0 + int(a), y0 + int(b)): (bool(av), int(v)) for a, b, av, v in zip(dx, dy, avail, vals)}
+                img = _NS(check_availability=lambda xc, yc, xn, yn: lut[(xn, yn)][0],
+                          get_ctu=lambda xn, yn: _NS(
+                              get_pred_mode=lambda x, y: 1,
+                              get_leaf_cu=lambda x, y: _NS(get_reconstructed_sample=lambda xx, yy, c: lut[(xx, yy)][1])))
+                cu = _NS(ctx=_NS(sps=sps, img=img, pps=_NS(constrained_intra_pred_flag=0)), MODE_INTRA=1)
+                pu = intra.IntraPu(cu, 0, mode, int(np.log2(n)), x0, y0)
+                with contextlib.redirect_stdout(io.StringIO()):
+                    nb = pu.decode_neighbor(x0, y0, int(np.log2(n)), 0)
+                out, _ = _ref_predict(intra, sps, _plain(nb, n), n, mode, 0)
+                for k, v in zip(("n", "mode", "pattern", "vals", "avail", "out"),
+                                (n, mode, pi, vals, avail, out.reshape(-1))):
+                    chain[k].append(v)
+
+    cat = lambda lst, t: np.concatenate([np.asarray(a).reshape(-1) for a in lst]).astype(t)
+    for a in vert["out"] + m10["out"] + chain["out"]:
+        assert a.min() >= 0 and a.max() < (1 << bd)
+    f_pins = os.path.join(HERE, "ref_pins%s.npz" % tag)
+    np.savez_compressed(f_pins, vert_n=np.array(vert["n"], np.uint8), vert_mode=np.array(vert["mode"], np.uint8),
+                        vert_c=np.array(vert["c"], np.uint8), vert_L=cat(vert["L"], dt), vert_out=cat(vert["out"], dt),
+                        m10_n=np.array(m10["n"], np.uint8), m10_L=cat(m10["L"], dt), m10_out=cat(m10["out"], dt))
+    f_chain = os.path.join(HERE, "ref_chain%s.npz" % tag)
+    np.savez_compressed(f_chain, chain_n=np.array(chain["n"], np.uint8), chain_mode=np.array(chain["mode"], np.uint8),
+                        chain_pattern=np.array(chain["pattern"], np.uint8), chain_vals=cat(chain["vals"], dt),
+                        chain_avail=cat(chain["avail"], np.uint8), chain_out=cat(chain["out"], dt))
+    meta = dict(generator="tests/golden/gen_component_fixture.py --pins", seed=[SEED, 2, bd], bit_depth=bd,
+                cases=dict(vertical=len(vert["n"]), mode10=len(m10["n"]), mode10_clipped=clips, chain=len(chain["n"])),
+                chain_patterns=[p for p, _ in CHAIN_PATTERNS], styles=list(PIN_STYLES), strong_intra_smoothing=1,
+                functions=["intra.py:161-181 (horizontal branch, on transposed neighbours, for modes 19..25, 27..34)",
+                           "intra.py:138-160 (mode 26, on transposed neighbours, for luma mode 10 below 32x32)",
+                           "intra.py:186-305 decode_neighbor", "intra.py:82-122 planar / DC"],
+                ref_components_npz_sha256_unchanged=old,
+                npz_sha256={os.path.basename(f): hashlib.sha256(open(f, "rb").read()).hexdigest() for f in (f_pins, f_chain)})
+    for f in (f_pins, f_chain):
+        assert os.path.getsize(f) <= 322083, "%s: %d bytes" % (f, os.path.getsize(f))
+    with open(os.path.join(HERE, "ref_pins%s.json" % tag), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    print(json.dumps(meta, indent=1))
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--bit-depth", type=int, default=8, choices=(8, 10, 12))
     ap.add_argument("--scaling", action="store_true", help="the ScalingFactor vectors (ref_scaling.npz) instead")
+    ap.add_argument("--pins", action="store_true", help="the transposition and chain vectors (ref_pins / ref_chain) instead")
     args = ap.parse_args()
     if args.scaling:
         main_scaling()
+    elif args.pins:
+        main_pins(args.bit_depth)
     else:
         main(args.bit_depth)
