@@ -4,7 +4,8 @@ ARCH ?= gfx950
 # -structurizecfg-skip-uniform-regions: uniform branches stay plain scalar branches (no i1 flow masks in
 # SGPR pairs): row kernel 4.70 -> 4.21 ms per 512 1080p pictures (tools/ab_libs2.sh, round 3)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wall -Wno-unused-function -mllvm -structurizecfg-skip-uniform-regions=true
-SRC := p265_amd/csrc/p265r.hip
+# (sparse_host.cpp: the host-only part of the sparse coefficient upload, plain C++ -- see sparse-check)
+SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp
 HDR := $(wildcard p265_amd/csrc/*.h) include/p265r.h
 
 CXX ?= g++
@@ -43,10 +44,18 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS)
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
+
+# host sanitizer check of the sparse upload's host code (sparsify + record validation, malformed inputs
+# included): a stand-alone CPU program, not part of `all`
+sparse-check: tools/sparse_check.cpp p265_amd/csrc/sparse_host.cpp p265_amd/csrc/sparse_host.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o tools/sparse_check tools/sparse_check.cpp p265_amd/csrc/sparse_host.cpp
+	./tools/sparse_check
+.PHONY: sparse-check
 
 # experiment builds: make variant V=name FLAGS="-DX=1"  ->  p265_amd/libp265r_name.so
 variant:

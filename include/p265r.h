@@ -114,8 +114,9 @@ typedef struct p265r_tb {
     uint8_t  flags;           /* P265R_TB_*                                                    */
     uint8_t  qp;              /* qP for scaling: Qp'Y or Qp'Cb / Qp'Cr (incl. QpBdOffset); luma
                                  TBs (PCM ones too) also give QpY + QpBdOffsetY to deblocking    */
-    uint8_t  reserved[3];
-    uint32_t coef_off;        /* int16 offset of the N*N TransCoeffLevel[y][x] (iff CBF|PCM)   */
+    uint8_t  reserved[3];     /* 0; sparse upload: [0..1] = the TB's entry count, little-endian  */
+    uint32_t coef_off;        /* int16 offset of the N*N TransCoeffLevel[y][x] (iff CBF|PCM);
+                                 sparse upload, transformed TBs: index of the TB's first entry  */
 } p265r_tb;
 
 /* One picture of a batch (host memory, caller-owned). */
@@ -144,6 +145,13 @@ typedef struct p265r_picture {
     uint32_t         reserved;
 } p265r_picture;
 
+/* Sparse coefficients of one picture (parallel to pics[i]).  Entry = pos | (uint16_t)level << 16,
+ * pos = y * N + x inside its TB (raster, N = 1 << log2_size), level the int16 TransCoeffLevel. */
+typedef struct p265r_sparse_coef {
+    const uint32_t* nz;
+    uint64_t        n_nz;
+} p265r_sparse_coef;
+
 /* Per-phase device time of the last run, from HIP events on the context's stream. */
 typedef struct p265r_timings {
     double   total_ms;        /* first kernel start -> last kernel end                     */
@@ -166,6 +174,32 @@ void p265r_destroy(p265r_ctx* ctx);
 /* Validate the records of n_pics pictures and copy them (plus output planes) into a
  * device-resident batch.  Synchronous w.r.t. the host buffers. */
 int  p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p265r_batch** out);
+/* The same upload with the coefficients of the transformed blocks given as their non-zero levels
+ * (opt-in; the dense call above stays the default).  sp[i] goes with pics[i].  A TB with P265R_TB_CBF
+ * and neither P265R_TB_PCM nor P265R_TB_BYPASS (the transform classes and transform skip) is SPARSE:
+ * its coef_off is the index of its first entry in sp[i].nz, its entry count the little-endian uint16
+ * in reserved[0..1] (0 .. N*N; reserved[2] = 0), its entries contiguous with strictly increasing pos
+ * (a level of 0 is allowed); positions not listed are 0.  PCM and bypass TBs keep the dense meaning:
+ * coef_off into pics[i].coef (NULL / empty when the picture has none); every TB that is not sparse has
+ * a count of 0.  Every record is checked on the host before anything reaches the device
+ * (P265R_ERANGE: entries outside sp[i].nz, pos >= N*N; P265R_EINVAL: count > N*N, positions not
+ * increasing, reserved[2] set, a count on a TB that is not sparse, sp or a needed nz NULL).  The
+ * device expands the entries into the batch's coefficient pool at upload time: the batch is
+ * afterwards the one the dense upload of the same coefficients gives, byte for byte, and runs the
+ * same.  Uploads fewer bytes when few levels are non-zero (4 bytes per entry + 4 per sparse TB
+ * against 2 per position).  No counterpart in the reference. */
+int  p265r_batch_upload_sparse(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_coef* sp,
+                               int n_pics, p265r_batch** out);
+/* Host only (no context, no device): the sparse form of a dense picture.  tbs_out gets pic->n_tbs
+ * records (sparse TBs: coef_off / count as above; PCM and bypass TBs: coef_off into raw_out, their
+ * N*N samples compacted in TB order; reserved zeroed), nz_out the entries, raw_out the samples;
+ * n_nz / n_raw get the counts.  With tbs_out, nz_out and raw_out all NULL only the counts are
+ * returned; otherwise P265R_ERANGE when a capacity (nz_cap entries, raw_cap samples) is too small. */
+int  p265r_sparsify(const p265r_picture* pic, p265r_tb* tbs_out, uint32_t* nz_out, uint64_t nz_cap,
+                    uint64_t* n_nz, int16_t* raw_out, uint64_t raw_cap, uint64_t* n_raw);
+/* Bytes of the host-to-device copies the batch's upload enqueued (dense or sparse: for comparing
+ * the two).  No counterpart in the reference. */
+int  p265r_batch_upload_bytes(p265r_ctx* ctx, p265r_batch* batch, uint64_t* h2d_bytes);
 /* Enqueue reconstruction + SAO of every picture of the batch on the context stream. */
 int  p265r_batch_run(p265r_ctx* ctx, p265r_batch* batch);
 /* Wait for the batch and copy its planes into pics[i].out / pics[i].recon; returns what

@@ -57,6 +57,10 @@ class PictureC(ctypes.Structure):
                 ("pic_width", ctypes.c_uint16), ("pic_height", ctypes.c_uint16), ("reserved", ctypes.c_uint32)]
 
 
+class SparseCoefC(ctypes.Structure):
+    _fields_ = [("nz", ctypes.c_void_p), ("n_nz", ctypes.c_uint64)]
+
+
 class Timings(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("residual_ms", ctypes.c_double), ("intra_ms", ctypes.c_double),
                 ("sao_ms", ctypes.c_double), ("intra_launches", ctypes.c_int32),
@@ -72,6 +76,11 @@ SIGNATURES = {
     "p265r_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Params), ctypes.POINTER(_vp)]),
     "p265r_destroy": (None, [_vp]),
     "p265r_batch_upload": (ctypes.c_int, [_vp, ctypes.POINTER(PictureC), ctypes.c_int, ctypes.POINTER(_vp)]),
+    "p265r_batch_upload_sparse": (ctypes.c_int, [_vp, ctypes.POINTER(PictureC), ctypes.POINTER(SparseCoefC), ctypes.c_int,
+                                                 ctypes.POINTER(_vp)]),
+    "p265r_sparsify": (ctypes.c_int, [ctypes.POINTER(PictureC), _vp, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                      _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "p265r_batch_upload_bytes": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
     "p265r_batch_run": (ctypes.c_int, [_vp, _vp]),
     "p265r_batch_download": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(PictureC), ctypes.c_int]),
     "p265r_batch_status": (ctypes.c_int, [_vp, _vp]),

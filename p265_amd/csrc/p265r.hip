@@ -30,9 +30,11 @@
 #include "loopfilter16.h"
 #include "sao16.h"
 #include "residual.h"
+#include "coef_expand.h"
 #include "sao.h"
 #include "sao_strip16.h"
 #include "sao_rows.h"
+#include "sparse_host.h"
 #include "tables.h"
 
 using namespace p265r;
@@ -61,6 +63,11 @@ using namespace p265r;
 #ifndef P265R_UP_STREAM
 #define P265R_UP_STREAM 0          // 0: a batch uploads on its own lane stream; 1: on an upload stream created with
                                    // the context; 2: created at the first upload (after the lanes)
+#endif
+#ifndef P265R_EXPAND_STREAM
+#define P265R_EXPAND_STREAM 0      // sparse upload: 0 the expand kernels follow their chunk's copies on the upload's
+                                   // stream; 1 (A/B) on a second stream gated by an event per chunk, beside the next
+                                   // chunk's copies
 #endif
 #ifndef P265R_SPLIT_W16
 #define P265R_SPLIT_W16 1          // small split batches: W = 16 row kernel (0: the by-run W, A/B)
@@ -186,6 +193,13 @@ struct p265r_ctx {
     uint8_t* d_sf = nullptr;           // scaling lists: the intra ScalingFactor table (p265r_set_scaling_factors)
     unsigned char* dl_stage = nullptr;  // pinned download bounce buffer, 2 x kDlHalf (first download)
     hipEvent_t dl_ev[2] = {nullptr, nullptr};
+    // sparse upload (p265r_batch_upload_sparse): device landing buffer of a batch's entries and per-job
+    // entry begins (grow-only; an upload is complete when it returns, so the next one reuses it)
+    void* sp_mem = nullptr;
+    size_t sp_bytes = 0;
+    hipStream_t exp_stream = nullptr;       // P265R_EXPAND_STREAM: the expand kernels' stream
+    std::vector<hipEvent_t> exp_ev;         // ... its per-chunk gates (+ one join), and the timed uploads' event pairs
+    double last_expand_ms = -1.0;           // expand kernels of the last sparse upload (timing on), p265r_describe
 };
 
 struct p265r_batch {
@@ -210,6 +224,7 @@ struct p265r_batch {
     int* d_xg_prog = nullptr;  // cross-group row kernel (intra_rows.h XgBuf): progress words (zeroed per run
     uint8_t* d_xg_lines = nullptr;  // with the CU slots), the rows' bottom lines; null: batch too large
     std::vector<std::array<int, 2>> size;   // per picture: luma width, height
+    uint64_t h2d_bytes = 0;    // host-to-device bytes its upload enqueued (p265r_batch_upload_bytes)
     int runs = 0;              // p265r_batch_run calls so far
     hipEvent_t sao_done = nullptr;     // P265R_SAO_AUX: recorded on the aux stream after a run's loop filters
     bool sao_pending = false;          // ... and not yet joined into the lane stream (join_sao)
@@ -256,7 +271,9 @@ std::array<int, 2> pic_size(const p265r_ctx* ctx, const p265r_picture& pic) {
             pic.pic_height ? (int)pic.pic_height : (int)ctx->params.pic_height};
 }
 
-int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic) {
+// (sparse: the picture of a sparse upload -- its transformed TBs' coef_off index entries, checked by
+// sparse_validate_tb in the upload's counting pass)
+int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic, bool sparse = false) {
     const p265r_params& p = ctx->params;
     const auto sz = pic_size(ctx, pic);
     const int pw = sz[0], ph = sz[1];
@@ -300,7 +317,7 @@ int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic) {
             if (xl + nl > pw || yl + nl > ph) return P265R_ERANGE;
             if (xl < cx0 || yl < cy0 || xl + nl > cx0 + ctb || yl + nl > cy0 + ctb) return P265R_ERANGE;
             if ((t.x & 3) || (t.y & 3) || (t.x & (n - 1)) || (t.y & (n - 1))) return P265R_EINVAL;
-            if (t.flags & (P265R_TB_CBF | P265R_TB_PCM)) {
+            if ((t.flags & (P265R_TB_CBF | P265R_TB_PCM)) && !(sparse && tb_is_sparse(t))) {
                 if ((uint64_t)t.coef_off + (uint64_t)n * n > pic.n_coef) return P265R_ERANGE;
             }
             if (t.flags & ~0x0fu) return P265R_EINVAL;
@@ -645,12 +662,23 @@ void p265r_destroy(p265r_ctx* ctx) {
     if (ctx->cache_mem) (void)hipFree(ctx->cache_mem);
     if (ctx->d_sf) (void)hipFree(ctx->d_sf);
     if (ctx->dl_stage) (void)hipHostFree(ctx->dl_stage);
+    if (ctx->sp_mem) (void)hipFree(ctx->sp_mem);
+    if (ctx->exp_stream) { (void)hipStreamSynchronize(ctx->exp_stream); (void)hipStreamDestroy(ctx->exp_stream); }
+    for (hipEvent_t e : ctx->exp_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->dl_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stage) { if (ctx->stage_pinned) (void)hipHostFree(ctx->stage); else std::free(ctx->stage); }
     delete ctx;
 }
 
-int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p265r_batch** out) {
+}  // extern "C"
+
+namespace {
+
+// The upload of p265r_batch_upload (sp null: dense coefficients) and p265r_batch_upload_sparse (sp[i]: the
+// entries of pics[i]'s transformed TBs).  Layout, chunking, staging and the device image are the same; the
+// sparse one stages, per chunk, the entries of each class slab in job order and one entry-begin word per job
+// instead of the slabs, and expands them on the device after the chunk's copies (coef_expand.h).
+int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_coef* sp, int n_pics, p265r_batch** out) {
     if (!ctx || !pics || n_pics <= 0 || !out) return P265R_EINVAL;
 #if P265R_EXPERIMENTS
     // P265R_UPLOAD_TIMES=1 (experiments build): wall time of the upload's stages on stderr
@@ -684,6 +712,7 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
     std::vector<std::array<size_t, N_POOLS>> cnt_pool(n_pics);
     std::vector<std::array<int, RC_NUM>> cnt_job(n_pics);
     std::vector<int> crc(n_pics, 0);
+    std::vector<std::array<size_t, RC_NUM>> cnt_nz(sp ? n_pics : 0);    // sparse: entries per class
     parallel_for(n_pics, [&](int i) {
         // every record of every picture is checked (on up to 16 host threads: pictures are independent; the
         // first failing picture's code is returned), then its coded TBs are counted per class with
@@ -692,20 +721,31 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
         // (validate_picture checks the TBs the CTUs reference, by position); one pass per picture right
         // after its validation, while its TB array is still in the cache
         const p265r_picture& pic = pics[i];
-        if ((crc[i] = validate_picture(ctx, pic)) != 0) return;
+        if ((crc[i] = validate_picture(ctx, pic, sp != nullptr)) != 0) return;
+        // (sparse: every entry of every TB is checked here, on the host, in the same pass -- the expand
+        // kernel trusts pos)
+        if (sp && !sp[i].nz && sp[i].n_nz) { crc[i] = P265R_EINVAL; return; }
         std::array<size_t, N_POOLS> cp{};
         std::array<int, RC_NUM> cj{};
+        std::array<size_t, RC_NUM> cn{};
         for (uint32_t t = 0; t < pic.n_tbs; ++t) {
             const p265r_tb& tb = pic.tbs[t];
+            if (sp) {                                  // (a local code: crc's elements share cache lines)
+                const int rc = sparse_validate_tb(tb, sp[i].nz, sp[i].n_nz, pic.n_coef);
+                if (rc) { crc[i] = rc; return; }
+            }
             if (!(tb.flags & (P265R_TB_CBF | P265R_TB_PCM))) continue;
             if (tb.log2_size < 2 || tb.log2_size > 5) { crc[i] = P265R_EINVAL; return; }
-            if ((uint64_t)tb.coef_off + ((uint64_t)1 << (2 * tb.log2_size)) > pic.n_coef) { crc[i] = P265R_ERANGE; return; }
+            const bool sparse_tb = sp && tb_is_sparse(tb);
+            if (!sparse_tb && (uint64_t)tb.coef_off + ((uint64_t)1 << (2 * tb.log2_size)) > pic.n_coef) { crc[i] = P265R_ERANGE; return; }
             const int cls = tb_class(tb);
             cp[cls] += (size_t)1 << (2 * tb.log2_size);
             if (cls < RC_NUM) ++cj[cls];
+            if (sparse_tb) cn[cls] += tb_sparse_count(tb);
         }
         cnt_pool[i] = cp;
         cnt_job[i] = cj;
+        if (sp) cnt_nz[i] = cn;
     });
     for (int i = 0; i < n_pics; ++i)
         if (crc[i]) return crc[i];
@@ -772,9 +812,22 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
     P265R_UT("layout");
 
     // ---- host staging: [0, o_res) | jobs [o_jobs[0], o_ijobs) | no-filter maps, compact ---------
+    // (sparse: of the pool only the raw slab is staged, at o_pool; behind the no-filter maps follow, per
+    // chunk, the entries [class][job order] and the begin words [class][job + 1 closing word])
     const size_t jobs_bytes = o_ijobs - o_jobs[0];
-    const size_t s_jobs = o_res, s_nf = o_res + jobs_bytes;
-    const size_t stage_need = s_nf + nf_bytes * n_nf;
+    const size_t s_jobs = sp ? align_up(o_pool + sizeof(int16_t) * pool_sz[RC_RAW], 256) : o_res, s_nf = s_jobs + jobs_bytes;
+    // (16 chunks of 32 pictures at 512: the first H2D starts after 1/16 of the packing; 4 chunks measured
+    // 78 ms per 512 1080p pictures, H2D-bound from the first chunk on)
+    const int n_chunks = std::max(1, std::min(n_pics / 8, 16));
+    size_t nz_total = 0, n_jobs_total = 0;
+    for (int i = 0; sp && i < n_pics; ++i)
+        for (int c = 0; c < RC_NUM; ++c) nz_total += cnt_nz[i][c];
+    for (int c = 0; c < RC_NUM; ++c) n_jobs_total += (size_t)n_jobs[c];
+    if (nz_total > (size_t)UINT32_MAX) return P265R_ERANGE;         // begin words are 32-bit entry indices
+    const size_t beg_words = sp ? n_jobs_total + (size_t)n_chunks * RC_NUM : 0;
+    const size_t s_ent = align_up(s_nf + nf_bytes * n_nf, 256), s_beg = s_ent + align_up(sizeof(uint32_t) * nz_total, 256);
+    const size_t sp_need = sp ? align_up(sizeof(uint32_t) * nz_total, 256) + align_up(sizeof(uint32_t) * beg_words, 256) : 0;
+    const size_t stage_need = sp ? s_ent + sp_need : s_nf + nf_bytes * n_nf;
     (void)hipSetDevice(ctx->device);
     if (ctx->stage_bytes < stage_need) {
         if (ctx->stage) { if (ctx->stage_pinned) (void)hipHostFree(ctx->stage); else std::free(ctx->stage); }
@@ -813,6 +866,20 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
         }
         if (e != hipSuccess) { delete b; return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc"); }
         b->bytes = total;
+    }
+    if (sp && ctx->sp_bytes < sp_need) {                     // landing buffer of the entries + begin words
+        if (ctx->sp_mem) (void)hipFree(ctx->sp_mem);
+        ctx->sp_mem = nullptr;
+        ctx->sp_bytes = 0;
+        const size_t want = sp_need + sp_need / 4;
+        e = hipMalloc(&ctx->sp_mem, want);
+        if (e != hipSuccess) {
+            ctx->sp_mem = nullptr;
+            (void)hipFree(b->mem);
+            delete b;
+            return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc");
+        }
+        ctx->sp_bytes = want;
     }
     b->n_pics = n_pics;
     b->stream = ctx->stream;
@@ -863,6 +930,30 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
             nf += pics[i].nofilter ? 1 : 0;
         }
     }
+    auto chunk_lo = [&](int k) { return (int)((long long)n_pics * k / n_chunks); };
+    // sparse: where each picture's entries and begin words of every class go (chunk-major, then class, then
+    // picture), and where each chunk's class ranges start (ent_kc / beg_kc [k * RC_NUM + c]; [n_chunks * RC_NUM]
+    // closes the last)
+    std::vector<std::array<size_t, RC_NUM>> ent_at(sp ? n_pics : 0), beg_at(sp ? n_pics : 0);
+    std::vector<size_t> ent_kc, beg_kc;
+    if (sp) {
+        size_t ef = 0, bf = 0;
+        for (int k = 0; k < n_chunks; ++k)
+            for (int c = 0; c < RC_NUM; ++c) {
+                ent_kc.push_back(ef);
+                beg_kc.push_back(bf);
+                for (int i = chunk_lo(k); i < chunk_lo(k + 1); ++i) {
+                    ent_at[i][c] = ef; ef += cnt_nz[i][c];
+                    beg_at[i][c] = bf; bf += (size_t)cnt_job[i][c];
+                }
+                ++bf;                                            // the class range's closing word
+            }
+        ent_kc.push_back(ef);
+        beg_kc.push_back(bf);
+    }
+    uint32_t* h_ent = sp ? reinterpret_cast<uint32_t*>(host + s_ent) : nullptr;
+    uint32_t* h_beg = sp ? reinterpret_cast<uint32_t*>(host + s_beg) : nullptr;
+    int16_t* h_raw = reinterpret_cast<int16_t*>(host + o_pool);     // sparse: the raw slab alone
     auto pack_pic = [&](int i) {
         const p265r_picture& pic = pics[i];
         std::memcpy(h_ctus + (size_t)i * nc, pic.ctus, sizeof(p265r_ctu) * pnc[i]);
@@ -872,18 +963,28 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
         int job_fill[RC_NUM];
         for (int c = 0; c < N_POOLS; ++c) pool_fill[c] = pool_at[i][c];
         for (int c = 0; c < RC_NUM; ++c) job_fill[c] = job_at[i][c];
+        size_t ent_fill[RC_NUM] = {}, beg_fill[RC_NUM] = {};
+        for (int c = 0; sp && c < RC_NUM; ++c) { ent_fill[c] = ent_at[i][c]; beg_fill[c] = beg_at[i][c]; }
         for (uint32_t t = 0; t < pic.n_tbs; ++t) {
             p265r_tb tb = pic.tbs[t];
+            if (sp) std::memset(tb.reserved, 0, sizeof(tb.reserved));     // (the entry count: not part of the image)
             if (tb.flags & (P265R_TB_CBF | P265R_TB_PCM)) {
                 const int cls = tb_class(tb);
                 const size_t nn = (size_t)1 << (2 * tb.log2_size);
-                int16_t* dst = h_pool + pool_fill[cls];
-                const int16_t* src = pic.coef + tb.coef_off;
-                switch (tb.log2_size) {                // fixed sizes: inlined vector moves, no memcpy call per TB
-                    case 2: std::memcpy(dst, src, 16 * sizeof(int16_t)); break;
-                    case 3: std::memcpy(dst, src, 64 * sizeof(int16_t)); break;
-                    case 4: std::memcpy(dst, src, 256 * sizeof(int16_t)); break;
-                    default: std::memcpy(dst, src, 1024 * sizeof(int16_t)); break;
+                if (sp && cls < RC_NUM) {              // sparse TB: its entries + the index of the first
+                    const uint32_t cnt = tb_sparse_count(pic.tbs[t]);
+                    h_beg[beg_fill[cls]++] = (uint32_t)ent_fill[cls];
+                    if (cnt) std::memcpy(h_ent + ent_fill[cls], sp[i].nz + tb.coef_off, sizeof(uint32_t) * cnt);
+                    ent_fill[cls] += cnt;
+                } else {
+                    int16_t* dst = sp ? h_raw + (pool_fill[cls] - pool_base[RC_RAW]) : h_pool + pool_fill[cls];
+                    const int16_t* src = pic.coef + tb.coef_off;
+                    switch (tb.log2_size) {            // fixed sizes: inlined vector moves, no memcpy call per TB
+                        case 2: std::memcpy(dst, src, 16 * sizeof(int16_t)); break;
+                        case 3: std::memcpy(dst, src, 64 * sizeof(int16_t)); break;
+                        case 4: std::memcpy(dst, src, 256 * sizeof(int16_t)); break;
+                        default: std::memcpy(dst, src, 1024 * sizeof(int16_t)); break;
+                    }
                 }
                 tb.coef_off = (uint32_t)pool_fill[cls];
                 if (cls < RC_NUM) h_jobs[cls][job_fill[cls]++] = ResJob{tb.coef_off, tb.qp, tb.flags, tb.log2_size, tb.c_idx};
@@ -928,24 +1029,44 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
     (void)hipSetDevice(ctx->device);
     if (P265R_UP_STREAM == 2 && !ctx->up_stream && e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking);
     hipStream_t st = P265R_UP_STREAM ? ctx->up_stream : b->stream;
-    auto h2d = [&](size_t dev_off, size_t host_off, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(dbase + dev_off, host + host_off, bytes, hipMemcpyHostToDevice, st);
+    auto h2d_to = [&](void* dst, size_t host_off, size_t bytes) {
+        if (e == hipSuccess && bytes) {
+            e = hipMemcpyAsync(dst, host + host_off, bytes, hipMemcpyHostToDevice, st);
+            b->h2d_bytes += bytes;
+        }
     };
+    auto h2d = [&](size_t dev_off, size_t host_off, size_t bytes) { h2d_to(dbase + dev_off, host_off, bytes); };
     if (e == hipSuccess) e = hipMemsetAsync(dbase + o_res, 0, o_ijobs - o_res, st);   // residual pool, job lists
     if (e == hipSuccess) e = hipMemsetAsync(dbase + o_ijobs, 0, o_rec - o_ijobs, st);
-    // (16 chunks of 32 pictures at 512: the first H2D starts after 1/16 of the packing; 4 chunks measured
-    // 78 ms per 512 1080p pictures, H2D-bound from the first chunk on)
-    const int n_chunks = std::max(1, std::min(n_pics / 8, 16));
+    // sparse: the expand kernels of a chunk follow its copies -- on the same stream, or (P265R_EXPAND_STREAM) on
+    // a second one behind an event, beside the next chunk's copies; with timing on, an event pair per chunk
+    unsigned char* d_sp = static_cast<unsigned char*>(ctx->sp_mem);
+    const uint32_t* d_ent = reinterpret_cast<const uint32_t*>(d_sp);
+    const uint32_t* d_beg = sp ? reinterpret_cast<const uint32_t*>(d_sp + (s_beg - s_ent)) : nullptr;
+    hipStream_t xs = st;
+    const bool time_expand = sp && ctx->timing;
+    enum { EV_JOIN = 16, EV_TIMED = 17, EV_NUM = 17 + 32 };      // [k]: chunk k's gate; [EV_TIMED + 2 k (+ 1)]: its timed pair
+    auto expand_event = [&](int idx) -> hipEvent_t {
+        if (ctx->exp_ev.empty()) ctx->exp_ev.resize(EV_NUM, nullptr);
+        if (!ctx->exp_ev[idx] && e == hipSuccess)
+            e = idx >= EV_TIMED ? hipEventCreate(&ctx->exp_ev[idx]) : hipEventCreateWithFlags(&ctx->exp_ev[idx], hipEventDisableTiming);
+        return ctx->exp_ev[idx];
+    };
+    if (sp && P265R_EXPAND_STREAM) {
+        if (!ctx->exp_stream && e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->exp_stream, hipStreamNonBlocking);
+        if (ctx->exp_stream) xs = ctx->exp_stream;
+    }
+    ctx->last_expand_ms = -1.0;
     for (int k = 0; k < n_chunks; ++k) {
-        const int p0 = (int)((long long)n_pics * k / n_chunks), p1 = (int)((long long)n_pics * (k + 1) / n_chunks);
+        const int p0 = chunk_lo(k), p1 = chunk_lo(k + 1);
         parallel_for(p1 - p0, [&](int j) { pack_pic(p0 + j); });
         h2d(o_ctus + sizeof(p265r_ctu) * nc * (size_t)p0, o_ctus + sizeof(p265r_ctu) * nc * (size_t)p0,
             sizeof(p265r_ctu) * nc * (size_t)(p1 - p0));
         const size_t t1 = p1 < n_pics ? tb_at[p1] : n_tbs_total;
         h2d(o_tbs + sizeof(p265r_tb) * tb_at[p0], o_tbs + sizeof(p265r_tb) * tb_at[p0], sizeof(p265r_tb) * (t1 - tb_at[p0]));
-        for (int c = 0; c < N_POOLS; ++c) {
+        for (int c = sp ? (int)RC_RAW : 0; c < N_POOLS; ++c) {
             const size_t q0 = pool_at[p0][c], q1 = p1 < n_pics ? pool_at[p1][c] : pool_base[c] + pool_sz[c];
-            h2d(o_pool + sizeof(int16_t) * q0, o_pool + sizeof(int16_t) * q0, sizeof(int16_t) * (q1 - q0));
+            h2d(o_pool + sizeof(int16_t) * q0, o_pool + sizeof(int16_t) * (sp ? q0 - pool_base[RC_RAW] : q0), sizeof(int16_t) * (q1 - q0));
         }
         for (int c = 0; c < RC_NUM; ++c) {
             const size_t j0 = (size_t)job_at[p0][c], j1 = p1 < n_pics ? (size_t)job_at[p1][c] : (size_t)n_jobs[c];
@@ -953,6 +1074,58 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
         }
         const size_t f1 = p1 < n_pics ? nf_at[p1] : n_nf;
         h2d(o_nf + nf_bytes * nf_at[p0], s_nf + nf_bytes * nf_at[p0], nf_bytes * (f1 - nf_at[p0]));
+        if (!sp) continue;
+        // the chunk's entries and begin words (each class range closed by the index past its last entry)
+        for (int c = 0; c < RC_NUM; ++c) h_beg[beg_kc[k * RC_NUM + c + 1] - 1] = (uint32_t)ent_kc[k * RC_NUM + c + 1];
+        const size_t e0 = ent_kc[k * RC_NUM], e1 = ent_kc[(k + 1) * RC_NUM], b0 = beg_kc[k * RC_NUM], b1 = beg_kc[(k + 1) * RC_NUM];
+        h2d_to(d_sp + sizeof(uint32_t) * e0, s_ent + sizeof(uint32_t) * e0, sizeof(uint32_t) * (e1 - e0));
+        h2d_to(d_sp + (s_beg - s_ent) + sizeof(uint32_t) * b0, s_beg + sizeof(uint32_t) * b0, sizeof(uint32_t) * (b1 - b0));
+        if (xs != st) {
+            hipEvent_t gate = expand_event(k);
+            if (e == hipSuccess) e = hipEventRecord(gate, st);
+            if (e == hipSuccess) e = hipStreamWaitEvent(xs, gate, 0);
+        }
+        if (time_expand) { hipEvent_t t0 = expand_event(EV_TIMED + 2 * k); if (e == hipSuccess) e = hipEventRecord(t0, xs); }
+        for (int c = 0; c < RC_NUM && e == hipSuccess; ++c) {
+            const size_t j0 = (size_t)job_at[p0][c], j1 = p1 < n_pics ? (size_t)job_at[p1][c] : (size_t)n_jobs[c];
+            const int nj = (int)(j1 - j0);
+            if (!nj) continue;
+            const uint32_t* beg = d_beg + beg_kc[k * RC_NUM + c];
+            const ResJob* jobs = b->d_jobs[c] + j0;
+            const size_t q0 = pool_at[p0][c];                    // = the slab offset of job j0
+#if P265R_EXPAND_SCATTER
+            const size_t q1 = p1 < n_pics ? pool_at[p1][c] : pool_base[c] + pool_sz[c];
+            e = hipMemsetAsync(b->d_pool + q0, 0, sizeof(int16_t) * (q1 - q0), xs);
+            if (e != hipSuccess) break;
+            switch (c) {
+                case RC_DST4: case RC_DCT4: case RC_TSKIP: coef_scatter_kernel<1><<<(nj + 255) / 256, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
+                case RC_DCT8: coef_scatter_kernel<4><<<(nj + 63) / 64, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
+                case RC_DCT16: coef_scatter_kernel<16><<<(nj + 15) / 16, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
+                default: coef_scatter_kernel<64><<<(nj + 3) / 4, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
+            }
+#else
+            const int per_block = kExpandWaves * kExpandTile;    // int16 per block of a fixed-size class
+            switch (c) {
+                case RC_DST4: case RC_DCT4:
+                    coef_expand_kernel<2><<<(unsigned)(((size_t)nj * 16 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
+                case RC_DCT8:
+                    coef_expand_kernel<3><<<(unsigned)(((size_t)nj * 64 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
+                case RC_DCT16:
+                    coef_expand_kernel<4><<<(unsigned)(((size_t)nj * 256 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
+                case RC_DCT32:
+                    coef_expand_kernel<5><<<(unsigned)(((size_t)nj * 1024 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
+                default:
+                    coef_expand_jobs_kernel<<<(unsigned)((nj + kExpandWaves - 1) / kExpandWaves), 64 * kExpandWaves, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
+            }
+#endif
+            e = hipGetLastError();
+        }
+        if (time_expand) { hipEvent_t t1e = expand_event(EV_TIMED + 2 * k + 1); if (e == hipSuccess) e = hipEventRecord(t1e, xs); }
+    }
+    if (xs != st) {                                              // the upload's stream waits for the last expand
+        hipEvent_t join = expand_event(EV_JOIN);
+        if (e == hipSuccess) e = hipEventRecord(join, xs);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
     }
     P265R_UT("pack");
     std::memcpy(host + o_pics, b->h_pics.data(), sizeof(DevPic) * n_pics);
@@ -984,22 +1157,62 @@ int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p2
                 const int wd[3] = {psize[i][0], psize[i][0] / 2, psize[i][0] / 2}, ht[3] = {psize[i][1], psize[i][1] / 2, psize[i][1] / 2};
                 e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, pics[i].recon[c], wd[c] * pb, wd[c] * pb, ht[c],
                                      hipMemcpyHostToDevice, st);
+                b->h2d_bytes += (size_t)wd[c] * pb * ht[c];
             }
     }
     P265R_UT("enqueue");
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     P265R_UT("h2d");
+    if (time_expand && e == hipSuccess) {
+        double ms = 0;
+        for (int k = 0; k < n_chunks && e == hipSuccess; ++k) {
+            float t = 0;
+            e = hipEventElapsedTime(&t, ctx->exp_ev[EV_TIMED + 2 * k], ctx->exp_ev[EV_TIMED + 2 * k + 1]);
+            ms += t;
+        }
+        if (e == hipSuccess) ctx->last_expand_ms = ms;
+    }
 #if P265R_EXPERIMENTS
     if (ut) {
-        fprintf(stderr, "[p265r] upload %d pictures, %.1f MB staged:", n_pics, (double)(o_res + jobs_bytes) / 1e6);
+        fprintf(stderr, "[p265r] %s upload %d pictures, %.1f MB copied:", sp ? "sparse" : "dense", n_pics, (double)b->h2d_bytes / 1e6);
         for (size_t i = 1; i < tp.size(); ++i)
             fprintf(stderr, " %s %.2f ms", tp[i].first, std::chrono::duration<double, std::milli>(tp[i].second - tp[i - 1].second).count());
         fprintf(stderr, "\n");
     }
 #endif
 #undef P265R_UT
-    if (e != hipSuccess) { int rc = hip_fail(e, "upload"); (void)hipFree(b->mem); delete b; return rc; }
+    if (e != hipSuccess) {
+        // copies (and expand kernels) enqueued before the failing call may still be in flight: let them end
+        // before the allocation they write is freed
+        int rc = hip_fail(e, "upload");
+        (void)hipStreamSynchronize(st);
+        if (xs != st) (void)hipStreamSynchronize(xs);
+        (void)hipFree(b->mem);
+        delete b;
+        return rc;
+    }
     *out = b;
+    return P265R_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p265r_batch_upload(p265r_ctx* ctx, const p265r_picture* pics, int n_pics, p265r_batch** out) {
+    return upload_batch(ctx, pics, nullptr, n_pics, out);
+}
+
+int p265r_batch_upload_sparse(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_coef* sp, int n_pics,
+                              p265r_batch** out) {
+    if (out) *out = nullptr;
+    if (!sp) return P265R_EINVAL;
+    return upload_batch(ctx, pics, sp, n_pics, out);
+}
+
+int p265r_batch_upload_bytes(p265r_ctx* ctx, p265r_batch* b, uint64_t* h2d_bytes) {
+    if (!ctx || !b || !h2d_bytes) return P265R_EINVAL;
+    *h2d_bytes = b->h2d_bytes;
     return P265R_OK;
 }
 
@@ -1535,6 +1748,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
         "\"pipeline\": %d, \"fork_prep\": %d, \"pipe_waves\": %d, \"hw_queues\": \"%s\", \"num_cus\": %d, \"diag_build\": %d, "
         "\"experiments_build\": %d, \"split\": %d, \"last_launch_split\": %d, \"xg\": %d, \"last_launch_xg\": %d, "
         "\"phase_order\": %d, \"early_residual\": %d, \"bit_depth\": %d, \"row_launches\": {\"w12\": %lld, \"w8\": %lld, \"w16_split\": %lld, \"xg\": %lld, \"other\": %lld}, "
+        "\"sparse_expand\": \"%s\", \"sparse_expand_stream\": %d, \"last_sparse_expand_ms\": %.4f, "
         "\"env_overrides\": [%s]}",
         ctx->schedule ? "rows" : "steps", ctx->row_waves,
         ctx->row_waves ? "fixed" : (P265R_PHASE_ORDER
@@ -1556,6 +1770,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
 #endif
         P265R_EXPERIMENTS, ctx->split, ctx->last_split ? 1 : 0, ctx->xg, ctx->last_xg ? 1 : 0, P265R_PHASE_ORDER, P265R_EARLY_RESIDUAL,
         (int)ctx->params.bit_depth_luma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], ctx->row_launches[4],
+        P265R_EXPAND_SCATTER ? "memset + global scatter" : "lds tile", P265R_EXPAND_STREAM, ctx->last_expand_ms,
         ctx->describe.c_str());
     if (n < 0) return P265R_EINVAL;
     if (size > 0) {

@@ -168,7 +168,8 @@ DEFAULT_BATCH, DEFAULT_DEPTH, DEFAULT_CHUNK = 8, 4, 1 << 20
 
 def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT_BATCH, threads: int = 0,
                   verify_hash: bool = True, min_batch: int = 8, prefetch: int = 4, depth: int = DEFAULT_DEPTH,
-                  stats: Optional[StageTimes] = None, cache_contexts: bool = True) -> Iterator[DecodedFrame]:
+                  stats: Optional[StageTimes] = None, cache_contexts: bool = True,
+                  sparse_upload: bool = False) -> Iterator[DecodedFrame]:
     """Decode a stream given as an iterable of byte chunks; yields frames in output order.
 
     Three stages run concurrently: the parse thread (native front-end on its own host threads),
@@ -177,7 +178,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     them) and the caller's thread (downloads, checks the picture hashes on a host pool, emits in
     output order).  Batches alternate over ``depth`` back-end contexts, so batch k+1 uploads
     while batch k is downloaded; at most ``depth`` batches are in flight.  Contexts stay warm
-    between calls (``cache_contexts``; ``release_contexts()`` frees them)."""
+    between calls (``cache_contexts``; ``release_contexts()`` frees them).  ``sparse_upload``: the
+    coefficients go up as their non-zero levels (ReconContext.upload(sparse=True)); the output is the same."""
     import time
     clock = time.perf_counter
     if not threads:
@@ -240,7 +242,7 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             return
         with lane.lock:
             t0 = clock()
-            b = lane.ctx.upload([d.picture for d in group])     # records -> HBM
+            b = lane.ctx.upload([d.picture for d in group], sparse=sparse_upload)     # records -> HBM
             t1 = clock()
             lane.ctx.run(b)                                     # enqueued; decodes meanwhile
         st.add("upload", t1 - t0)

@@ -29,6 +29,29 @@ def _params_c(p):
     return c
 
 
+def sparsify(pic):
+    """records.SparsePicture of a dense Picture through the C p265r_sparsify (host only: needs the
+    library, no context and no device; records.sparsify is the numpy statement of the same)."""
+    lib = _lib.load()
+    tbs_in = np.ascontiguousarray(pic.tbs, R.TB_DTYPE)
+    coef = np.ascontiguousarray(pic.coef, np.int16)
+    c = _lib.PictureC()
+    c.tbs = tbs_in.ctypes.data if len(tbs_in) else None
+    c.n_tbs = len(tbs_in)
+    c.coef = coef.ctypes.data if len(coef) else None
+    c.n_coef = len(coef)
+    n_nz, n_raw = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(lib.p265r_sparsify(ctypes.byref(c), None, None, 0, ctypes.byref(n_nz), None, 0, ctypes.byref(n_raw)),
+               "p265r_sparsify")
+    tbs = np.zeros(len(tbs_in), R.TB_DTYPE)
+    nz = np.zeros(n_nz.value, np.uint32)
+    raw = np.zeros(n_raw.value, np.int16)
+    _lib.check(lib.p265r_sparsify(ctypes.byref(c), tbs.ctypes.data, nz.ctypes.data, len(nz), ctypes.byref(n_nz),
+                                  raw.ctypes.data, len(raw), ctypes.byref(n_raw)), "p265r_sparsify")
+    return R.SparsePicture(ctus=pic.ctus, tbs=tbs, nz=nz, coef=raw, nofilter=pic.nofilter, size=pic.size,
+                           recon_input=pic.recon_input, meta=dict(pic.meta))
+
+
 def plane_shapes(params):
     w, h = int(params["pic_width"]), int(params["pic_height"])
     return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
@@ -160,11 +183,35 @@ class ReconContext:
         return [[np.empty(s, dt) for s, dt in zip(plane_shapes(R.pic_params(self.params, p)), dts)] for p in pics]
 
     # ---- batch API --------------------------------------------------------------
-    def upload(self, pics):
-        arr, keep = self._pictures_c(pics)
+    def upload(self, pics, sparse=False):
+        """Records -> a device-resident batch.  ``sparse``: the coefficients of the transformed TBs go up
+        as their non-zero entries and are expanded on the device (p265r_batch_upload_sparse); ``pics`` are
+        then records.SparsePicture, or Picture (sparsified here through p265r_sparsify).  The batch is the
+        same either way."""
+        if not sparse:
+            arr, keep = self._pictures_c(pics)
+            h = ctypes.c_void_p()
+            _lib.check(self.lib.p265r_batch_upload(self.handle, arr, len(pics), ctypes.byref(h)), "p265r_batch_upload")
+            return Batch(self, h, pics, keep)
+        sps = [p if isinstance(p, R.SparsePicture) else sparsify(p) for p in pics]
+        arr, keep = self._pictures_c(sps)
+        sc = (_lib.SparseCoefC * len(sps))()
+        for i, p in enumerate(sps):
+            nz = np.ascontiguousarray(p.nz, np.uint32)
+            keep.append(nz)
+            sc[i].nz = nz.ctypes.data if len(nz) else None
+            sc[i].n_nz = len(nz)
         h = ctypes.c_void_p()
-        _lib.check(self.lib.p265r_batch_upload(self.handle, arr, len(pics), ctypes.byref(h)), "p265r_batch_upload")
+        _lib.check(self.lib.p265r_batch_upload_sparse(self.handle, arr, sc, len(sps), ctypes.byref(h)),
+                   "p265r_batch_upload_sparse")
         return Batch(self, h, pics, keep)
+
+    def upload_bytes(self, batch):
+        """Host-to-device bytes the batch's upload enqueued (p265r_batch_upload_bytes)."""
+        n = ctypes.c_uint64(0)
+        _lib.check(self.lib.p265r_batch_upload_bytes(self.handle, batch.handle, ctypes.byref(n)),
+                   "p265r_batch_upload_bytes")
+        return int(n.value)
 
     def run(self, batch):
         _lib.check(self.lib.p265r_batch_run(self.handle, batch.handle), "p265r_batch_run")
@@ -280,7 +327,18 @@ class ReconContext:
         return {f: getattr(t, f) for f, _ in _lib.Timings._fields_ if f != "reserved"}
 
     # ---- one-shot API (submit / wait) -------------------------------------------------
-    def decode(self, pics, with_recon=False):
+    def decode(self, pics, with_recon=False, sparse=False):
+        """Upload, run and download in one call.  ``sparse``: through the sparse upload (the submit / wait
+        pair of the C ABI is dense; this is upload(sparse=True) + run + download)."""
+        if sparse:
+            b = self.upload(pics, sparse=True)
+            try:
+                self.run(b)
+                wr = with_recon and pics[0].recon_input is None
+                res = self.download(b, with_recon=wr)
+                return (res, None) if with_recon and not wr else res
+            finally:
+                b.free()
         outs = self._alloc_planes(pics)
         recs = self._alloc_planes(pics) if with_recon and pics[0].recon_input is None else None
         arr, keep = self._pictures_c(pics, outs, recs)

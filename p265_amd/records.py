@@ -145,6 +145,104 @@ class RecordError(ValueError):
     pass
 
 
+@dataclass
+class SparsePicture:
+    """A picture whose transformed TBs carry their coefficients as entries (include/p265r.h
+    p265r_sparse_coef, p265r_batch_upload_sparse): ``nz`` uint32 entries pos | (uint16)level << 16,
+    ``tbs`` with coef_off = first entry and the entry count in reserved[0..1] for sparse TBs (CBF
+    without PCM / bypass), coef_off into ``coef`` (the PCM / bypass samples alone) for the others."""
+    ctus: np.ndarray
+    tbs: np.ndarray
+    nz: np.ndarray                         # uint32
+    coef: np.ndarray                       # int16: raw (PCM / bypass) samples only
+    nofilter: Optional[np.ndarray] = None
+    size: Optional[tuple] = None
+    recon_input: Optional[list] = None
+    meta: dict = field(default_factory=dict)
+    # the dense coef_off of every TB of the picture sparsify() was given, so that densify() restores that
+    # layout exactly (a picture built tile by tile keeps its coefficients in tile-scan order); None: TB order
+    dense_off: Optional[np.ndarray] = None
+
+
+def _tb_kinds(tbs):
+    """(sparse, raw) masks of a TB array: coded through a transform (or transform skip) / coded PCM or
+    bypass (dense by nature)."""
+    f = tbs["flags"]
+    dense_kind = (f & (TB_PCM | TB_BYPASS)) != 0
+    return ((f & TB_CBF) != 0) & ~dense_kind, ((f & (TB_CBF | TB_PCM)) != 0) & dense_kind
+
+
+def _ranges(starts, lengths):
+    """Concatenated aranges start[i] .. start[i] + length[i], and the index i of every element."""
+    lengths = lengths.astype(np.int64)
+    owner = np.repeat(np.arange(len(lengths)), lengths)
+    first = np.cumsum(lengths) - lengths
+    within = np.arange(int(lengths.sum()), dtype=np.int64) - np.repeat(first, lengths)
+    return np.repeat(starts.astype(np.int64), lengths) + within, owner, within
+
+
+def sparsify(pic: Picture) -> SparsePicture:
+    """The sparse form of a dense picture (what the C p265r_sparsify computes): the non-zero levels of
+    every transformed TB in raster order, the PCM / bypass samples compacted in TB order."""
+    tbs = pic.tbs.copy()
+    tbs["reserved"] = 0
+    dense_off = pic.tbs["coef_off"].copy()
+    coef = np.ascontiguousarray(pic.coef, np.int16)
+    sparse, raw = _tb_kinds(tbs)
+    nn = 1 << (2 * tbs["log2_size"].astype(np.int64))
+    if ((tbs["coef_off"].astype(np.int64) + nn)[sparse | raw] > len(coef)).any():
+        raise RecordError("coefficient range outside coef array")
+    si = np.flatnonzero(sparse)
+    idx, owner, pos = _ranges(tbs["coef_off"][si], nn[si])
+    val = coef[idx]
+    keep = val != 0
+    nz = (pos[keep].astype(np.uint32) | (val[keep].view(np.uint16).astype(np.uint32) << 16)).astype(np.uint32)
+    count = np.bincount(owner[keep], minlength=len(si)).astype(np.int64)
+    tbs["coef_off"][si] = np.cumsum(count) - count
+    tbs["reserved"][si, 0] = count & 0xff
+    tbs["reserved"][si, 1] = count >> 8
+    ri = np.flatnonzero(raw)
+    ridx, _, _ = _ranges(tbs["coef_off"][ri], nn[ri])
+    tbs["coef_off"][ri] = np.cumsum(nn[ri]) - nn[ri]
+    return SparsePicture(ctus=pic.ctus, tbs=tbs, nz=nz, coef=coef[ridx], nofilter=pic.nofilter, size=pic.size,
+                         recon_input=pic.recon_input, meta=dict(pic.meta), dense_off=dense_off)
+
+
+def densify(sp: SparsePicture) -> Picture:
+    """The dense picture of a sparse one: every coded TB's N*N values at the offsets sparsify() found
+    them (``dense_off``: densify(sparsify(pic)) == pic), else packed in TB order."""
+    tbs = sp.tbs.copy()
+    sparse, raw = _tb_kinds(tbs)
+    nn = 1 << (2 * tbs["log2_size"].astype(np.int64))
+    coded = sparse | raw
+    off = np.zeros(len(tbs), np.int64)
+    off[coded] = np.cumsum(nn[coded]) - nn[coded]
+    n_coef = int(nn[coded].sum())
+    if sp.dense_off is not None:
+        off = sp.dense_off.astype(np.int64)
+        n_coef = int((off + nn)[coded].max()) if coded.any() else 0
+    coef = np.zeros(n_coef, np.int16)
+    si = np.flatnonzero(sparse)
+    count = tbs["reserved"][si, 0].astype(np.int64) | (tbs["reserved"][si, 1].astype(np.int64) << 8)
+    eidx, owner, _ = _ranges(tbs["coef_off"][si], count)
+    if len(eidx) and int(eidx.max()) >= len(sp.nz):
+        raise RecordError("entry range outside the entry array")
+    ent = np.ascontiguousarray(sp.nz, np.uint32)[eidx]
+    pos = (ent & 0xffff).astype(np.int64)
+    if (pos >= nn[si][owner]).any():
+        raise RecordError("entry position outside its TB")
+    coef[off[si][owner] + pos] = (ent >> 16).astype(np.uint16).view(np.int16)
+    ri = np.flatnonzero(raw)
+    ridx, rowner, rpos = _ranges(tbs["coef_off"][ri], nn[ri])
+    if len(ridx) and int(ridx.max()) >= len(sp.coef):
+        raise RecordError("raw sample range outside coef array")
+    coef[off[ri][rowner] + rpos] = np.ascontiguousarray(sp.coef, np.int16)[ridx]
+    tbs["coef_off"] = np.where(coded | (sp.dense_off is not None), off, tbs["coef_off"])
+    tbs["reserved"] = 0
+    return Picture(ctus=sp.ctus, tbs=tbs, coef=coef, nofilter=sp.nofilter, meta=dict(sp.meta),
+                   recon_input=sp.recon_input, size=sp.size)
+
+
 def check_shapes(params, pic: Picture):
     """The checks the C ABI cannot do itself (array dtypes and lengths behind the raw
     pointers); everything inside the records is validated again by p265r_batch_upload."""
