@@ -113,7 +113,9 @@ typedef struct p265r_tb {
     uint8_t  pred_mode;       /* IntraPredModeY / IntraPredModeC, 0..34                        */
     uint8_t  flags;           /* P265R_TB_*                                                    */
     uint8_t  qp;              /* qP for scaling: Qp'Y or Qp'Cb / Qp'Cr (incl. QpBdOffset); luma
-                                 TBs (PCM ones too) also give QpY + QpBdOffsetY to deblocking    */
+                                 TBs (PCM ones too) also give QpY + QpBdOffsetY to deblocking.
+                                 0 .. 51 + 6 * (BitDepth of the component - 8), PCM TBs included:
+                                 anything larger is P265R_EINVAL at upload                        */
     uint8_t  reserved[3];     /* 0; sparse upload: [0..1] = the TB's entry count, little-endian  */
     uint32_t coef_off;        /* int16 offset of the N*N TransCoeffLevel[y][x] (iff CBF|PCM);
                                  sparse upload, transformed TBs: index of the TB's first entry  */

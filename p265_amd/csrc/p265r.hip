@@ -271,6 +271,13 @@ std::array<int, 2> pic_size(const p265r_ctx* ctx, const p265r_picture& pic) {
             pic.pic_height ? (int)pic.pic_height : (int)ctx->params.pic_height};
 }
 
+// p265r_tb.qp (qP incl. QpBdOffset of the TB's component) is 0 .. 51 + 6 * (BitDepth - 8) (8.6.1).  PCM TBs
+// too: a luma TB's qp goes into the deblocking map entry beside the edge bits (dbk_map_kernel: one byte at 8
+// bits, where 64 and above would set them), and a coded TB's qp / 6 sets Dequant's shift (residual.h).
+inline bool qp_ok(const p265r_params& p, const p265r_tb& t) {
+    return t.qp <= 51 + 6 * ((t.c_idx ? p.bit_depth_chroma : p.bit_depth_luma) - 8);
+}
+
 // (sparse: the picture of a sparse upload -- its transformed TBs' coef_off index entries, checked by
 // sparse_validate_tb in the upload's counting pass)
 int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic, bool sparse = false) {
@@ -311,6 +318,7 @@ int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic, bool sparse
             if (t.c_idx && ++n_chroma > 2 * (ctb / 8) * (ctb / 8)) return P265R_EINVAL;  // kMaxCtuChroma
             if (t.log2_size < 2 || t.log2_size > 5 || t.c_idx > 2 || t.pred_mode > 34) return P265R_EINVAL;
             if (t.c_idx && t.log2_size > 4) return P265R_EINVAL;        // 4:2:0 chroma TBs are 4..16
+            if (!qp_ok(p, t)) return P265R_EINVAL;
             const int sub = t.c_idx ? 1 : 0;
             const int n = 1 << t.log2_size;
             const int xl = t.x << sub, yl = t.y << sub, nl = n << sub;
@@ -735,7 +743,7 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
                 if (rc) { crc[i] = rc; return; }
             }
             if (!(tb.flags & (P265R_TB_CBF | P265R_TB_PCM))) continue;
-            if (tb.log2_size < 2 || tb.log2_size > 5) { crc[i] = P265R_EINVAL; return; }
+            if (tb.log2_size < 2 || tb.log2_size > 5 || tb.c_idx > 2 || !qp_ok(ctx->params, tb)) { crc[i] = P265R_EINVAL; return; }
             const bool sparse_tb = sp && tb_is_sparse(tb);
             if (!sparse_tb && (uint64_t)tb.coef_off + ((uint64_t)1 << (2 * tb.log2_size)) > pic.n_coef) { crc[i] = P265R_ERANGE; return; }
             const int cls = tb_class(tb);

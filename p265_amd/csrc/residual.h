@@ -45,10 +45,13 @@ __device__ __forceinline__ int clamp16i(int v) {
 }
 
 // d = Clip3(-32768, 32767, (L * 16 * levelScale[qP%6] << (qP/6) + (1 << (bdShift-1))) >> bdShift)
-// computed exactly in 32 bits with the shift pair folded: |L| <= 2^15 and 16 * 72 < 2^11 give
-// |L * scale| < 2^26 (one 24-bit multiply), and lshift = qP/6 - bdShift <= 8 - 5 = 3 (8-bit video:
-// qP <= 51, bdShift >= 5; p265r_create rejects other bit depths), so the shifted product stays
-// below 2^29.  (Round 2 widened it to 64 bits: ~10 VALU per coefficient instead of 5.)
+// computed exactly in 32 bits with the shift pair folded, for BitDepth 8..12 (p265r_create rejects other
+// depths): |L| <= 2^15 and 16 * 72 < 2^11 give |L * scale| < 2^26 (one 24-bit multiply).  The upload rejects
+// qP > 51 + 6 * (BitDepth - 8) = 6 * BitDepth + 3 (validate_picture), so qP/6 <= BitDepth, and bdShift =
+// BitDepth + log2 - 5 >= BitDepth - 3: lshift = qP/6 - bdShift <= 3 (reached by 4x4 TBs at the top four
+// qP of every depth), scale << 3 < 2^14 and the shifted product stays below 2^29.  The right
+// shift bdShift - qP/6 is at most 12 (32x32 at 12 bits, qP < 6).  (Round 2 widened it to 64 bits: ~10 VALU
+// per coefficient instead of 5.)
 struct Dequant {
     int scale, lshift, rshift, rnd;
     __device__ __forceinline__ Dequant(int qp, int bd_shift) {

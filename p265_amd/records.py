@@ -290,6 +290,9 @@ def validate(params, pic: Picture):
     cc = np.concatenate([[0], np.cumsum(tbs["c_idx"] != 0)])
     if ((cc[end] - cc[begin]) > 2 * (1 << (2 * (ctb_log2 - 3)))).any():
         raise RecordError("CTU lists more chroma TBs than it has 4x4 chroma units")
+    qp_max = np.where(c > 0, 51 + qp_bd_offset(params, 1), 51 + qp_bd_offset(params, 0))
+    if (tbs["qp"] > qp_max).any():
+        raise RecordError("TB qp above 51 + QpBdOffset of its component")
     sub = (c > 0).astype(np.int64)
     xl, yl = tbs["x"].astype(np.int64) << sub, tbs["y"].astype(np.int64) << sub
     nl = (1 << lg) << sub

@@ -18,6 +18,9 @@ planted_set(bit_depth) is the fixed set the CPU and GPU tests decode: every plac
 32} x 35 pictures, picture i with luma mode i and chroma mode (i + 17) % 35; at ``interior`` once per
 neighbour style (NEIGHBOUR_STYLES), the styles rotating over the other placements; the residual styles
 (RESIDUAL_STYLES) rotate everywhere.
+
+residual_set(bit_depth), further down, is the planted residual set: the same builder at ``interior`` on a constant
+prediction, with chosen coefficients, qP and flags.
 """
 import os
 
@@ -123,14 +126,18 @@ def _residual(rng, style, log2, sign):
 
 
 def build(s, placement, luma_modes, chroma_mode, bit_depth, neighbours=None, nxn=False, residual="none",
-          seed=0, sign=1, meta=None):
+          seed=0, sign=1, meta=None, qp_y=30, coefs=None, tskip=(0, 0, 0), bypass=False, chroma_qp_offsets=(0, 0)):
     """-> (params, records.Picture) of one planted picture.
 
     ``luma_modes``: one mode, or four for an NxN CU (S = 8 only).  ``neighbours``: [luma, Cb, Cr] linear
     reference arrays (4N + 1 each, N = S for luma and S / 2 for chroma, or 4 for the first luma block of an
     NxN CU; ref_positions order) for the reference lines, each or all None for seeded random ones.
     ``residual``: RESIDUAL_STYLES; ``sign``: sign of the saturating DC level of luma and Cr (Cb takes the
-    opposite one).
+    opposite one).  ``qp_y``: QpY of every CU (-QpBdOffsetY..51); the chroma qP follow from it and
+    ``chroma_qp_offsets`` (Cb, Cr) through frontend.chroma_qp.  ``coefs``: [luma, Cb, Cr] TransCoeffLevel arrays
+    [y][x] of the target's TBs instead of a residual style, each None for an uncoded TB; at an NxN CU the luma
+    array is the first 4x4 block's (the three others, which do not predict from the planted reference lines,
+    stay uncoded).  ``tskip``: transform_skip_flag per component; ``bypass``: cu_transquant_bypass_flag.
     """
     size_of, at_of, new_slice, tile_cols, _ = PLACEMENTS[placement]
     (w, h), (x0, y0) = size_of(s), at_of(s)
@@ -152,26 +159,33 @@ def build(s, placement, luma_modes, chroma_mode, bit_depth, neighbours=None, nxn
             ok = (xs >= 0) & (ys >= 0) & (xs < pw) & (ys < ph)
             planes[c][ys[ok], xs[ok]] = np.asarray(neighbours[c])[ok]
     offy, offc = R.qp_bd_offset(params, 0), R.qp_bd_offset(params, 1)
-    qcb, qcr = frontend.chroma_qp(30, 0, 0, offc)
-    qps = (30 + offy, qcb + offc, qcr + offc)
+    qcb, qcr = frontend.chroma_qp(qp_y, chroma_qp_offsets[0], chroma_qp_offsets[1], offc)
+    qps = (qp_y + offy, qcb + offc, qcr + offc)
     b = frontend.PictureBuilder(params)
 
     def target():
         if nxn:
             tus = []
             for i in range(4):
-                co = [_residual(rng, residual, 2, sign if i % 2 == 0 else -sign), None, None]
-                if i == 3:
-                    co[1], co[2] = _residual(rng, residual, 2, -sign), _residual(rng, residual, 2, sign)
+                if coefs is not None:
+                    co = [coefs[0] if i == 0 else None, coefs[1] if i == 3 else None, coefs[2] if i == 3 else None]
+                else:
+                    co = [_residual(rng, residual, 2, sign if i % 2 == 0 else -sign), None, None]
+                    if i == 3:
+                        co[1], co[2] = _residual(rng, residual, 2, -sign), _residual(rng, residual, 2, sign)
                 tus.append(dict(x=x0 + 4 * (i % 2), y=y0 + 4 * (i // 2), log2=2, blk=i,
-                                cbf=[int(v is not None) for v in co], tskip=[0, 0, 0], coef=co))
-            b.add_cu(x0, y0, 3, 1, modes, int(chroma_mode), *qps, tus)
+                                cbf=[int(v is not None) for v in co], tskip=[int(v) for v in tskip], coef=co))
+            b.add_cu(x0, y0, 3, 1, modes, int(chroma_mode), *qps, tus, bypass=bypass)
             return
         lg = s.bit_length() - 1
-        co = [_residual(rng, residual, lg, sign), _residual(rng, residual, max(lg - 1, 2), -sign),
-              _residual(rng, residual, max(lg - 1, 2), sign)]
-        tu = dict(x=x0, y=y0, log2=lg, blk=0, cbf=[int(v is not None) for v in co], tskip=[0, 0, 0], coef=co)
-        b.add_cu(x0, y0, lg, 0, modes, int(chroma_mode), *qps, [tu])
+        if coefs is not None:
+            co = list(coefs)
+        else:
+            co = [_residual(rng, residual, lg, sign), _residual(rng, residual, max(lg - 1, 2), -sign),
+                  _residual(rng, residual, max(lg - 1, 2), sign)]
+        tu = dict(x=x0, y=y0, log2=lg, blk=0, cbf=[int(v is not None) for v in co], tskip=[int(v) for v in tskip],
+                  coef=co)
+        b.add_cu(x0, y0, lg, 0, modes, int(chroma_mode), *qps, [tu], bypass=bypass)
 
     def node(x, y, log2):
         n = 1 << log2
@@ -209,10 +223,11 @@ def target_region(pic, c_idx):
     return slice(y0 >> sub, (y0 + s) >> sub), slice(x0 >> sub, (x0 + s) >> sub)
 
 
-def set_params(bit_depth):
-    """The parameter set a context decodes the whole planted set with (pictures carry their own size)."""
+def set_params(bit_depth, scaling=False):
+    """The parameter set a context decodes the whole planted set with (pictures carry their own size);
+    ``scaling``: with scaling_list_enabled (the context is then given a ScalingFactor table)."""
     return R.make_params(pic_width=MAX_W, pic_height=MAX_H, ctb_log2_size=6, sample_adaptive_offset=0,
-                         bit_depth_luma=bit_depth, bit_depth_chroma=bit_depth)
+                         bit_depth_luma=bit_depth, bit_depth_chroma=bit_depth, scaling_list_enabled=int(scaling))
 
 
 def plan():
@@ -304,3 +319,242 @@ def chain_region(pic):
     x0, y0 = pic.meta["target"]
     n = pic.meta["n"]
     return slice(y0, y0 + n), slice(x0, x0 + n)
+
+
+# ---------------------------------------------------------------------------------
+# the planted residual set: chosen coefficients, qP and flags on a constant prediction
+# ---------------------------------------------------------------------------------
+# Every picture is the ``interior`` placement with every reference sample of the target set to one value v,
+# so every mode predicts the constant v and the target holds clip(v + r): a residual r is observed in full
+# where v + r stays inside the sample range, and by its sign where it does not (which tells a clamp from a
+# wrap).  residual_set(bit_depth) is the fixed set:
+#
+#   impulse   one non-zero level at every (ky, kx) of luma 32x32 / 16x16 / 8x8 / 4x4 (DST, NxN CU), the Cb and
+#             Cr TBs of the same picture carrying impulses at positions of their own, so that every (ky, kx) of
+#             chroma 16x16 / 8x8 / 4x4 occurs too; qP'Y = 30 + QpBdOffset, v = mid, the level the largest whose
+#             response at the TB's qP' stays strictly inside the sample range (impulse_level);
+#   sweep     a seeded synth._coef_block per TB at every qP'Y = 0 .. 51 + QpBdOffset for each size; Cb at the
+#             chroma qP of cb_qp_offset 0 and Cr at that of +12, which together take every qP'C as well;
+#   extreme   EXTREME_PATTERNS at qP' in {0, 29, max} and v in {0, max};
+#   tskip     4x4 transform skip, luma and chroma, levels -32768, 32767, 1, -1 at qP' 0 and max (of all three);
+#   bypass    transform-quant bypass at every size, levels -32768, 32767, max sample value and its negative;
+#   count     8x8 CUs that code chroma 4x4 TBs alone (Cb and Cr, or Cb only), for job_count_batches.
+#
+# The pictures with ``scaled`` in their meta (sweep and extreme) are decoded once more in contexts with scaling
+# lists (scaling_tables).
+
+RES_CLASSES = ("dst4", "dct4", "dct8", "dct16", "dct32")             # the residual kernels' job classes
+RES_TPB = {"dst4": 256, "dct4": 256, "dct8": 32, "dct16": 16, "dct32": 8}   # TBs per 256-thread block
+EXTREME_PATTERNS = ("pos", "neg", "checker", "colsign", "colsign_neg")
+V_NAMES = ("zero", "mid", "max")
+
+
+def res_class(log2, c_idx):
+    return "dst4" if (log2 == 2 and c_idx == 0) else "dct%d" % (1 << log2)
+
+
+def _v_of(name, bit_depth):
+    return {"zero": 0, "mid": 1 << (bit_depth - 1), "max": (1 << bit_depth) - 1}[name]
+
+
+def _impulse(n, ky, kx, level):
+    co = np.zeros((n, n), np.int16)
+    co[ky, kx] = level
+    return co
+
+
+def _impulse_inside(level, log2, c_idx, bit_depth, qp, positions):
+    n, mid = 1 << log2, 1 << (bit_depth - 1)
+    for ky, kx in positions:
+        for sg in (1, -1):
+            r = O.residual_block(_impulse(n, ky, kx, sg * level), log2, c_idx, qp, R.TB_CBF, bit_depth)
+            if r.min() <= -mid or r.max() >= mid - 1:              # 0 < mid + r < max
+                return False
+    return True
+
+
+_LEVELS = {}
+
+
+def impulse_level(log2, c_idx, bit_depth, qp):
+    """The largest level whose response in the Python oracle at qP' ``qp``, at any (ky, kx) and with either
+    sign, stays strictly inside the sample range around v = mid (bisected on the lowest four frequencies each
+    way, which hold the largest matrix entries, then stepped down until every position passes)."""
+    key = (log2, c_idx, bit_depth, qp)
+    if key not in _LEVELS:
+        n = 1 << log2
+        low = [(a, b) for a in range(4) for b in range(4)]
+        lo, hi = 1, 32767                                           # inside at lo, not known inside at hi + 1
+        while lo < hi:
+            m = (lo + hi + 1) // 2
+            lo, hi = (m, hi) if _impulse_inside(m, log2, c_idx, bit_depth, qp, low) else (lo, m - 1)
+        every = [(a, b) for a in range(n) for b in range(n)]
+        while not _impulse_inside(lo, log2, c_idx, bit_depth, qp, every):
+            lo -= 1
+        assert lo >= 1
+        _LEVELS[key] = lo
+    return _LEVELS[key]
+
+
+def extreme_block(pattern, log2, c_idx):
+    """EXTREME_PATTERNS: all +32767; all -32768; a +-32767 checkerboard; every column 32767 * sign(M[:, 0]) (M
+    the TB's transform matrix: the first output of stage 1 is the largest sum there is, in every column) and
+    its negative."""
+    n = 1 << log2
+    if pattern == "pos":
+        return np.full((n, n), 32767, np.int16)
+    if pattern == "neg":
+        return np.full((n, n), -32768, np.int16)
+    if pattern == "checker":
+        ys, xs = np.mgrid[0:n, 0:n]
+        return np.where((ys + xs) % 2 == 0, 32767, -32767).astype(np.int16)
+    m = O.transform_matrix(log2, 1 if (log2 == 2 and c_idx == 0) else 0)
+    col = np.where(m[:, 0] >= 0, 32767, -32767)
+    blk = np.repeat(col[:, None], n, axis=1)
+    return (blk if pattern == "colsign" else -blk).astype(np.int16)
+
+
+def _cycle_block(n, values):
+    return np.resize(np.asarray(values, np.int64), n * n).reshape(n, n).astype(np.int16)
+
+
+def chroma_qps(qp_prime, bit_depth):
+    """(qP'Cb, qP'Cr) of the residual set's pictures at luma qP' ``qp_prime``: cb_qp_offset 0, cr_qp_offset 12."""
+    off = 6 * (bit_depth - 8)
+    qcb, qcr = frontend.chroma_qp(qp_prime - off, 0, 12, off)
+    return qcb + off, qcr + off
+
+
+def residual_build(k, s, nxn, bit_depth, v_name, qp_prime, coefs, kind, tskip=(0, 0, 0), bypass=False, scaled=False,
+                   meta=None, chroma_qp_offsets=(0, 12)):
+    """One picture of the residual set: target CU of size ``s`` at ``interior`` on the constant ``v_name``,
+    luma qP' ``qp_prime``, Cb at cb_qp_offset 0 and Cr at +12 unless given; the modes rotate with ``k``."""
+    v = _v_of(v_name, bit_depth)
+    nc = max(s // 2, 4)
+    nb = [np.full(4 * s + 1, v), np.full(4 * nc + 1, v), np.full(4 * nc + 1, v)]
+    m = dict(kind=kind, v=v, scaled=bool(scaled), qp_prime=int(qp_prime))
+    m.update(meta or {})
+    modes = [(k + 9 * j) % 35 for j in range(4)] if nxn else k % 35
+    return build(s, "interior", modes, (k + 17) % 35, bit_depth, nb, nxn=nxn, seed=200000 + k, meta=m,
+                 qp_y=qp_prime - 6 * (bit_depth - 8), coefs=coefs, tskip=tskip, bypass=bypass,
+                 chroma_qp_offsets=chroma_qp_offsets)
+
+
+_RES_SETS = {}
+
+
+def residual_set(bit_depth):
+    """[(params, Picture)] of the fixed residual set at one bit depth (built once per process)."""
+    if bit_depth in _RES_SETS:
+        return _RES_SETS[bit_depth]
+    bd, pics = bit_depth, []
+    qp_max = 51 + 6 * (bd - 8)
+    mx = (1 << bd) - 1
+
+    def add(*a, **kw):
+        pics.append(residual_build(len(pics), *a, **kw))
+
+    for s, nxn in SIZES:                                                # impulses
+        lg = 2 if nxn else s.bit_length() - 1
+        lgc = max(s.bit_length() - 2, 2)
+        n, nc = 1 << lg, 1 << lgc
+        qp = 30 + 6 * (bd - 8)
+        lv, (lvb, lvr) = impulse_level(lg, 0, bd, qp), (impulse_level(lgc, c + 1, bd, q) for c, q in enumerate(chroma_qps(qp, bd)))
+        for k in range(n * n):
+            ky, kx = k // n, k % n
+            pb, pr = k % (nc * nc), (k + nc * nc // 2 + 1) % (nc * nc)
+            sb = 1 if ((k // (nc * nc)) + pb) % 2 == 0 else -1
+            co = [_impulse(n, ky, kx, lv if (ky + kx) % 2 == 0 else -lv), _impulse(nc, pb // nc, pb % nc, sb * lvb),
+                  _impulse(nc, pr // nc, pr % nc, -sb * lvr)]
+            add(s, nxn, bd, "mid", qp, co, "impulse")
+    for s_idx, (s, nxn) in enumerate(SIZES):                            # qP sweep
+        lg = 2 if nxn else s.bit_length() - 1
+        lgc = max(s.bit_length() - 2, 2)
+        rng = np.random.default_rng([11, s_idx])
+        co = [synth._coef_block(rng, lg, 0.2), synth._coef_block(rng, lgc, 0.2), synth._coef_block(rng, lgc, 0.2)]
+        for qp in range(qp_max + 1):
+            add(s, nxn, bd, V_NAMES[(qp + s_idx) % 3], qp, co, "sweep", scaled=True)
+    for s, nxn in SIZES:                                                # extremes
+        lg = 2 if nxn else s.bit_length() - 1
+        lgc = max(s.bit_length() - 2, 2)
+        for i, pat in enumerate(EXTREME_PATTERNS):
+            pat_r = EXTREME_PATTERNS[(i + 1) % len(EXTREME_PATTERNS)]
+            co = [extreme_block(pat, lg, 0), extreme_block(pat, lgc, 1), extreme_block(pat_r, lgc, 2)]
+            for qp in (0, 29, qp_max):
+                for v_name in ("zero", "max"):
+                    add(s, nxn, bd, v_name, qp, co, "extreme", scaled=True, meta=dict(patterns=(pat, pat, pat_r)))
+    ts = _cycle_block(4, [-32768, 32767, 1, -1])                        # transform skip (4x4 only)
+    for qp in (0, qp_max):
+        for v_name in V_NAMES:
+            # (chroma offsets 0 at the bottom and 12 at the top: Cb and Cr are at qP' 0 and max with luma)
+            add(8, True, bd, v_name, qp, [ts, ts.T.copy(), ts[::-1].copy()], "tskip", tskip=(1, 1, 1),
+                chroma_qp_offsets=(12, 12) if qp else (0, 0))
+    for s, nxn in SIZES:                                                # transform-quant bypass
+        lg = 2 if nxn else s.bit_length() - 1
+        lgc = max(s.bit_length() - 2, 2)
+        for v_name in V_NAMES:
+            co = [_cycle_block(1 << lg, [-32768, 32767, mx, -mx]), _cycle_block(1 << lgc, [32767, -mx, -32768, mx]),
+                  _cycle_block(1 << lgc, [mx, -32768, -mx, 32767])]
+            add(s, nxn, bd, v_name, 30 + 6 * (bd - 8), co, "bypass", bypass=True)
+    rng = np.random.default_rng([11, 99])                               # chroma 4x4 alone, two TBs or one
+    cb, cr = synth._coef_block(rng, 2, 0.3), synth._coef_block(rng, 2, 0.3)
+    add(8, False, bd, "mid", 27 + 6 * (bd - 8), [None, cb, cr], "count", meta=dict(n_dct4=2))
+    add(8, False, bd, "mid", 33 + 6 * (bd - 8), [None, cr, None], "count", meta=dict(n_dct4=1))
+    _RES_SETS[bit_depth] = pics
+    return pics
+
+
+def planted_tbs(pic):
+    """The TB records of a residual-set picture that sit on the constant prediction and carry a residual: the
+    coded TBs that are not PCM."""
+    f = pic.tbs["flags"]
+    return pic.tbs[((f & R.TB_PCM) == 0) & ((f & R.TB_CBF) != 0)]
+
+
+def class_counts(pics):
+    """TBs per residual job class over a batch (transform-skip TBs are a class of their own, bypass TBs have
+    no residual job)."""
+    out = dict.fromkeys(RES_CLASSES, 0)
+    for pic in pics:
+        for t in planted_tbs(pic):
+            if not int(t["flags"]) & (R.TB_TSKIP | R.TB_BYPASS):
+                out[res_class(int(t["log2_size"]), int(t["c_idx"]))] += 1
+    return out
+
+
+def job_count_batches(bit_depth):
+    """[(class, n, indices into residual_set)]: sub-batches whose TB count in one residual job class is exactly
+    n, for n = 1, TPB - 1, TPB, TPB + 1 (the last block of residualN_kernel then has TPB - 1 inactive TBs, one,
+    none, and again TPB - 1; residual4_kernel's last block a tail).  The pictures are the sweep's of the size
+    whose luma TB is of the class (cycled when n exceeds their number), for chroma 4x4 the ``count`` ones."""
+    pics = residual_set(bit_depth)
+    pool = {}
+    for i, (_, pic) in enumerate(pics):
+        if pic.meta["kind"] == "sweep":
+            pool.setdefault("dst4" if pic.meta["nxn"] else "dct%d" % pic.meta["s"], []).append(i)
+        if pic.meta["kind"] == "count":
+            pool[("dct4", pic.meta["n_dct4"])] = i
+    out = []
+    for cls in RES_CLASSES:
+        for n in (1, RES_TPB[cls] - 1, RES_TPB[cls], RES_TPB[cls] + 1):
+            if cls == "dct4":
+                idx = [pool[("dct4", 2)]] * (n // 2) + [pool[("dct4", 1)]] * (n % 2)
+            else:
+                idx = [pool[cls][j % len(pool[cls])] for j in range(n)]
+            out.append((cls, n, idx))
+    return out
+
+
+def scaling_tables():
+    """ScalingFactor tables (the 2032-byte ABI array) the scaled pictures are decoded with: random factors
+    1..255; 1 everywhere but 255 at DC and at (N - 1, N - 1); 255 everywhere."""
+    rng = np.random.default_rng(12)
+    rand, corners, full = {}, {}, {}
+    for key in O.SF_OFFSETS:
+        n = 4 << key[0]
+        rand[key] = rng.integers(1, 256, (n, n))
+        corners[key] = np.ones((n, n), np.int64)
+        corners[key][0, 0] = corners[key][n - 1, n - 1] = 255
+        full[key] = np.full((n, n), 255, np.int64)
+    return {"random": O.scaling_factor_bytes(rand), "corners": O.scaling_factor_bytes(corners),
+            "all255": O.scaling_factor_bytes(full)}

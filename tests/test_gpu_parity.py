@@ -435,6 +435,46 @@ def test_invalid_records_rejected(recon_mod):
             ctx.decode([bad])
 
 
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_out_of_range_qp_rejected(recon_mod, bd):
+    """p265r_tb.qp is qP incl. QpBdOffset, 0 .. 51 + 6 * (BitDepth - 8): the largest legal value uploads and
+    decodes (every TB of a valid picture set to it, PCM ones too); one more, or 255, on one luma, chroma, PCM or
+    uncoded record is EINVAL at upload -- on the dense and on the sparse path, before any kernel is launched (a qp of
+    64 and above would set edge bits of the one-byte deblocking map entry, and shift Dequant's scale out of
+    range)."""
+    from oracle import c_oracle
+    from p265_amd import _lib
+    params = R.make_params(pic_width=64, pic_height=64, bit_depth_luma=bd, bit_depth_chroma=bd)
+    pic = synth.make_picture(params, 3, deblocking=True, pcm_rate=0.2)
+    top = 51 + 6 * (bd - 8)
+    flags = pic.tbs["flags"]
+    luma = int(np.nonzero((pic.tbs["c_idx"] == 0) & (flags & R.TB_CBF != 0) & (flags & R.TB_PCM == 0))[0][0])
+    chroma = int(np.nonzero((pic.tbs["c_idx"] > 0) & (flags & R.TB_CBF != 0) & (flags & R.TB_PCM == 0))[0][0])
+    pcm = int(np.nonzero((pic.tbs["c_idx"] == 0) & (flags & R.TB_PCM != 0))[0][0])
+    uncoded = int(np.nonzero((pic.tbs["c_idx"] == 0) & (flags & (R.TB_CBF | R.TB_PCM) == 0))[0][0])
+    ok = R.Picture(ctus=pic.ctus, tbs=pic.tbs.copy(), coef=pic.coef, nofilter=pic.nofilter)
+    ok.tbs["qp"] = top
+    R.validate(params, ok)
+    ref = c_oracle.decode(params, [ok])[0]
+    with recon_mod.ReconContext(params) as ctx:
+        for sparse in (False, True):
+            outs = ctx.decode([ok], sparse=sparse)
+            for c in range(3):
+                np.testing.assert_array_equal(outs[0][c], ref[1][c], err_msg="qp %d c%d sparse=%r" % (top, c, sparse))
+        runs = ctx.describe()
+        for k in (luma, chroma, pcm, uncoded):
+            for qp in (top + 1, 255):
+                bad = R.Picture(ctus=pic.ctus, tbs=pic.tbs.copy(), coef=pic.coef, nofilter=pic.nofilter)
+                bad.tbs["qp"][k] = qp
+                with pytest.raises(R.RecordError):
+                    R.validate(params, bad)
+                for sparse in (False, True):
+                    with pytest.raises(_lib.P265RError) as ei:
+                        ctx.upload([bad], sparse=sparse)
+                    assert ei.value.code == _lib.EINVAL, (k, qp, sparse)
+        assert ctx.describe() == runs              # refused at upload: nothing was launched
+
+
 def test_invalid_chroma_size_and_tb_count_rejected(recon_mod):
     """A 32x32 chroma TB (impossible in 4:2:0) and a CTU listing more TBs (or chroma TBs)
     than it has 4x4 units are EINVAL at upload, before anything reaches the GPU."""
