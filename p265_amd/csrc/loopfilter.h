@@ -86,11 +86,15 @@ __global__ __launch_bounds__(64) void dbk_map_kernel(const DevPic* __restrict__ 
 // ---------------------------------------------------------------------------------------
 // Filters on registers.  P[i][k] / Q[i][k]: sample i away from the edge on line k.
 // ---------------------------------------------------------------------------------------
+// HBD: 16-bit samples of bit depth bd (9..12): beta = beta' << (bd - 8), tC = tC' << (bd - 8) (8.7.2.5.3,
+// 8.7.2.5.5), clipping to (1 << bd) - 1; else 8-bit samples, bd unused (shift 0 and clip 255 are constants)
+template <bool HBD>
 __device__ __forceinline__ void dbk_luma_seg(int (&P)[4][4], int (&Q)[4][4], int qpp, int qpq, int boff, int toff,
-                                             bool nop, bool noq) {
+                                             bool nop, bool noq, int bd) {
+    const int sh = HBD ? bd - 8 : 0, maxv = HBD ? (1 << bd) - 1 : 255;
     const int qpl = (qpq + qpp + 1) >> 1;
-    const int beta = dbk_beta(min(max(qpl + 2 * boff, 0), 51));
-    const int tc = c_tc_table[min(max(qpl + 2 + 2 * toff, 0), 53)];          // bS = 2
+    const int beta = dbk_beta(min(max(qpl + 2 * boff, 0), 51)) << sh;
+    const int tc = (int)c_tc_table[min(max(qpl + 2 + 2 * toff, 0), 53)] << sh;   // bS = 2
     const int dp0 = abs(P[2][0] - 2 * P[1][0] + P[0][0]), dp3 = abs(P[2][3] - 2 * P[1][3] + P[0][3]);
     const int dq0 = abs(Q[2][0] - 2 * Q[1][0] + Q[0][0]), dq3 = abs(Q[2][3] - 2 * Q[1][3] + Q[0][3]);
     if (dp0 + dq0 + dp3 + dq3 >= beta) return;
@@ -123,38 +127,33 @@ __device__ __forceinline__ void dbk_luma_seg(int (&P)[4][4], int (&Q)[4][4], int
                 d = min(max(d, -tc), tc);
                 const int th = tc >> 1;
                 if (!nop) {
-                    P[0][k] = min(max(p0 + d, 0), 255);
-                    if (dep) P[1][k] = min(max(p1 + min(max((((p2 + p0 + 1) >> 1) - p1 + d) >> 1, -th), th), 0), 255);
+                    P[0][k] = min(max(p0 + d, 0), maxv);
+                    if (dep) P[1][k] = min(max(p1 + min(max((((p2 + p0 + 1) >> 1) - p1 + d) >> 1, -th), th), 0), maxv);
                 }
                 if (!noq) {
-                    Q[0][k] = min(max(q0 - d, 0), 255);
-                    if (deq) Q[1][k] = min(max(q1 + min(max((((q2 + q0 + 1) >> 1) - q1 - d) >> 1, -th), th), 0), 255);
+                    Q[0][k] = min(max(q0 - d, 0), maxv);
+                    if (deq) Q[1][k] = min(max(q1 + min(max((((q2 + q0 + 1) >> 1) - q1 - d) >> 1, -th), th), 0), maxv);
                 }
             }
         }
     }
 }
 
-__device__ __forceinline__ void dbk_chroma_line(int& p0, int p1, int& q0, int q1, int tc, bool nop, bool noq) {
+// one line of a chroma edge (bS = 2); tc from dbk_chroma_tc
+template <bool HBD>
+__device__ __forceinline__ void dbk_chroma_line(int& p0, int p1, int& q0, int q1, int tc, bool nop, bool noq, int bd) {
+    const int maxv = HBD ? (1 << bd) - 1 : 255;
     const int d = min(max((((q0 - p0) * 4) + p1 - q1 + 4) >> 3, -tc), tc);
-    const int np0 = min(max(p0 + d, 0), 255), nq0 = min(max(q0 - d, 0), 255);
+    const int np0 = min(max(p0 + d, 0), maxv), nq0 = min(max(q0 - d, 0), maxv);
     if (!nop) p0 = np0;
     if (!noq) q0 = nq0;
 }
 
-// packed unsigned 16-bit ops (two samples per dword); inline asm keeps them packed (the
-// compiler otherwise splits clamped / min forms into per-element compares)
-__device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ uint32_t pk_subsat_u16(uint32_t a, uint32_t b) {       // max(a - b, 0)
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+// tC of a chroma edge: QpC from the two sides' QpY and the component's pps offset (8.7.2.5.5)
+template <bool HBD>
+__device__ __forceinline__ int dbk_chroma_tc(int qpp, int qpq, int cqp, int toff, int bd) {
+    const int qpi = ((qpq + qpp + 1) >> 1) + cqp;
+    return (int)c_tc_table[min(max(qpc_table(qpi) + 2 + 2 * toff, 0), 53)] << (HBD ? bd - 8 : 0);
 }
 
 __device__ __forceinline__ int byte_of(uint32_t w, int b) { return (int)((w >> (8 * b)) & 0xffu); }
@@ -198,18 +197,123 @@ template <int CTBL> struct LfShape {
     static constexpr int threads(bool dbk) { return dbk && T1 > P265R_LF_DBK_THREADS ? P265R_LF_DBK_THREADS : T1; }
 };
 
-// grid (CTUs, pictures); DBK: deblock the window first (else the window is the SAO input as is)
-// XCD-aware block order: hardware block b runs on XCD b % 8 (observed round-robin,
-// MI355X_MICROARCH.md); logical unit (picture, CTB) = (b % 8) * per + b / 8, so each XCD
-// walks one contiguous raster range and the halo rows / columns its windows share with
-// the neighbouring CTBs are read from its own L2.
-__device__ __forceinline__ int xcd_unit(int b, int n_units) {
-    const int per = (n_units + 7) >> 3;
-    return (b & 7) * per + (b >> 3);
+// ---------------------------------------------------------------------------------------
+// Shared by the two window kernels: loopfilter_kernel below (8-bit samples, packed dwords in LDS) and
+// loopfilter16_kernel (loopfilter16.h, uint16_t samples).  They differ in the sample windows, the
+// sample access of the filters and the SAO stage.
+// ---------------------------------------------------------------------------------------
+struct LfWindow {
+    bool outside;               // the whole workgroup has no work (past the grid, or outside a ragged picture)
+    int pic, rs, rx, ry;        // picture, CTB (raster address in the picture's own raster, column, row)
+    int x0, y0;                 // the CTB's first luma sample
+};
+
+// block -> (picture, CTB), XCD-aware order.  Straight-line like strip_pos (sao.h): a workgroup past the grid
+// decodes the last unit and leaves at the caller's `if (w.outside) return;`, before any barrier.
+// g: the batch's geometry in, the picture's out (its own size in a ragged batch).  (Not a field of
+// LfWindow: loopfilter16_kernel indexes g.bd[c], which keeps g in memory, and must not take more with it.)
+template <int CTBL>
+__device__ __forceinline__ LfWindow lf_window(const DevPic* __restrict__ pics, Geo& g, int n_pics) {
+    LfWindow w;
+    const Geo gb = g;
+    const int n_ctus = gb.wc * gb.hc;
+    const int bunit = xcd_unit(blockIdx.x, n_ctus * n_pics);
+    w.outside = bunit >= n_ctus * n_pics;
+    const int unit = min(bunit, n_ctus * n_pics - 1);
+    w.pic = unit / n_ctus;
+    w.rs = unit - w.pic * n_ctus;
+    w.rx = w.rs % gb.wc;
+    w.ry = w.rs / gb.wc;
+    if (P265R_RAGGED && gb.ragged) {                              // this picture's size and CTU raster
+        g = pic_geo(gb, (uint32_t)__builtin_amdgcn_readfirstlane((int)pics[w.pic].wh));
+        w.outside = w.outside || w.rx >= g.wc || w.ry >= g.hc;
+        w.rs = w.ry * g.wc + w.rx;
+    }
+    w.x0 = w.rx << CTBL;
+    w.y0 = w.ry << CTBL;
+    return w;
 }
 
-// grid (8 * ceil(CTUs * pictures / 8)); DBK: deblock the window first (else the window is
-// the SAO input as is)
+// CTU neighbourhood (s_ctu, DBK only), SAO permissions (s_allow, 8.7.3.2) and the windows of the
+// deblocking map (s_map, DBK only; M as dbk_map_kernel) and the nofilter map (s_nf): NB x NB 8x8 luma
+// blocks, one around the CTB.  T threads; the caller's barrier follows.
+template <typename M, int NB, bool DBK, int T>
+__device__ __forceinline__ void lf_fill_maps(const DevPic* P, const LfWindow& w, const Geo& g, const p265r_ctu& me, M* s_map,
+                                             uint8_t* s_nf, LfCtu* s_ctu, uint32_t* s_allow) {
+    const p265r_ctu* ctus = P->ctus;
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const bool ok = tid < 9 && sao_allow(ctus, me, w.rs, w.rx, w.ry, tid % 3 - 1, tid / 3 - 1, g);
+        const uint32_t bits = (uint32_t)__ballot(ok);
+        if (tid == 0) *s_allow = bits;
+        if (DBK && tid < 9) {
+            const int nx = w.rx + tid % 3 - 1, ny = w.ry + tid / 3 - 1;
+            LfCtu e{0xffffffffu, 0xffff, 0, 0};
+            if (nx >= 0 && ny >= 0 && nx < g.wc && ny < g.hc) {
+                const p265r_ctu& o = ctus[ny * g.wc + nx];
+                e = LfCtu{o.slice_addr, o.tile_id, o.flags, o.deblock_offsets};
+            }
+            s_ctu[tid] = e;
+        }
+    }
+    const int nf_h = (g.h + 7) >> 3;
+    for (int i = tid; i < NB * NB; i += T) {
+        const int bx = (w.x0 >> 3) - 1 + i % NB, by = (w.y0 >> 3) - 1 + i / NB;
+        const bool in = bx >= 0 && by >= 0 && bx < g.nf_w && by < nf_h;
+        const size_t o = (size_t)by * g.nf_w + bx;
+        if (DBK) s_map[i] = in ? reinterpret_cast<const M*>(P->dbk_map)[o] : 0;
+        s_nf[i] = in && P->nofilter ? P->nofilter[o] : 0;
+    }
+}
+
+// filterEdgeFlag for the edge between luma p0 (xp, yp) and q0 (xq, yq): Q's slice deblocking offsets, or -1
+template <int CTBL>
+__device__ __forceinline__ int dbk_edge_offs(const LfCtu* s_ctu, const LfWindow& w, const Geo& g, int xp, int yp, int xq, int yq) {
+    // slot of the CTU containing luma (x, y) in the 3x3 neighbourhood
+    auto slot = [&](int x, int y) { return ((y >> CTBL) - w.ry + 1) * 3 + (x >> CTBL) - w.rx + 1; };
+    const LfCtu q = s_ctu[slot(xq, yq)];
+    if (!(q.flags & P265R_CTU_DEBLOCK)) return -1;
+    const LfCtu p = s_ctu[slot(xp, yp)];
+    if (!g.lf_tiles && p.tile_id != q.tile_id) return -1;
+    if (p.slice_addr != q.slice_addr && !(q.flags & P265R_CTU_LF_ACROSS_SLICES)) return -1;
+    return q.offs;
+}
+
+// One deblocking task of direction dir (0: vertical edges, 1: horizontal): edge i (every 8 samples
+// from the CTB's first) and 4-line segment j (from 4 samples before the CTB) of a luma (sub 0) or
+// chroma (sub 1, 4:2:0) window.
+struct DbkEdge {
+    bool on;                    // inside the picture, a transform-block edge, and filtered (filterEdgeFlag)
+    int bp, bq;                 // s_map / s_nf entries of the 8x8 luma blocks of p0 and q0
+    int mq;                     // s_map[bq]
+    int offs;                   // Q's slice_beta_offset_div2 | slice_tc_offset_div2 << 4 (nibbles)
+};
+
+template <int CTBL, typename M, int NB>
+__device__ __forceinline__ DbkEdge dbk_edge_task(const LfWindow& w, const Geo& g, const M* s_map, const LfCtu* s_ctu, int dir,
+                                                 int sub, int i, int j) {
+    constexpr int ebit_v = sizeof(M) == 1 ? DBK_V : DBK16_V, ebit_h = sizeof(M) == 1 ? DBK_H : DBK16_H;
+    DbkEdge e;
+    e.on = false;
+    const int ge = ((dir ? w.y0 : w.x0) >> sub) + 8 * i;              // edge coordinate
+    const int gs = ((dir ? w.x0 : w.y0) >> sub) - 4 + 4 * j;          // segment start
+    const int We = sub ? g.cw : g.w, He = sub ? g.ch : g.h;
+    if (ge <= 0 || ge >= (dir ? He : We) || gs < 0 || gs >= (dir ? We : He)) return e;
+    const int xq = (dir ? gs : ge) << sub, yq = (dir ? ge : gs) << sub;       // luma position of q0
+    const int xp = dir ? xq : xq - 1, yp = dir ? yq - 1 : yq;
+    auto mblk = [&](int x, int y) { return ((y >> 3) - (w.y0 >> 3) + 1) * NB + (x >> 3) - (w.x0 >> 3) + 1; };
+    e.bq = mblk(xq, yq);
+    e.bp = mblk(xp, yp);
+    e.mq = s_map[e.bq];
+    if (!(e.mq & (dir ? ebit_h : ebit_v))) return e;
+    e.offs = dbk_edge_offs<CTBL>(s_ctu, w, g, xp, yp, xq, yq);
+    e.on = e.offs >= 0;
+    return e;
+}
+
+// grid (8 * ceil(CTUs * pictures / 8)), XCD-aware order (sao.h xcd_unit: each XCD walks one contiguous
+// raster range of (picture, CTB) units); DBK: deblock the window first (else the window is the SAO
+// input as is)
 template <int CTBL, bool DBK>
 __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel(const DevPic* __restrict__ pics, Geo g,
                                                                           int sao_on, int n_pics) {
@@ -226,47 +330,16 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
     __shared__ LfCtu s_ctu[9];
     __shared__ uint32_t s_allow;
 
-    const int n_ctus = g.wc * g.hc;
-    const int unit = xcd_unit(blockIdx.x, n_ctus * n_pics);
-    if (unit >= n_ctus * n_pics) return;                         // whole workgroup: before any barrier
-    const int pic = unit / n_ctus;
-    int rs = unit - pic * n_ctus;
-    const DevPic* P = pics + pic;
-    const p265r_ctu* ctus = P->ctus;
-    const int rx = rs % g.wc, ry = rs / g.wc;
-    if (P265R_RAGGED && g.ragged) {                                              // this picture's size and CTU raster
-        g = pic_geo(g, (uint32_t)__builtin_amdgcn_readfirstlane((int)P->wh));
-        if (rx >= g.wc || ry >= g.hc) return;                    // whole workgroup: before any barrier
-        rs = ry * g.wc + rx;
-    }
-    const int x0 = rx * S, y0 = ry * S, xc0 = x0 >> 1, yc0 = y0 >> 1;
+    const LfWindow w = lf_window<CTBL>(pics, g, n_pics);         // (g: this picture's from here on)
+    if (w.outside) return;                                       // whole workgroup: before any barrier
+    const DevPic* P = pics + w.pic;
+    const int x0 = w.x0, y0 = w.y0, xc0 = x0 >> 1, yc0 = y0 >> 1;
     const int tid = threadIdx.x;
     constexpr int T = SH::threads(DBK);
-    const p265r_ctu me = ctus[rs];
+    const p265r_ctu me = P->ctus[w.rs];
 
     // ---- CTU neighbourhood, SAO permissions (8.7.3.2), map windows, sample windows ---------------
-    if (tid < 64) {
-        const bool ok = tid < 9 && sao_allow(ctus, me, rs, rx, ry, tid % 3 - 1, tid / 3 - 1, g);
-        const uint32_t bits = (uint32_t)__ballot(ok);
-        if (tid == 0) s_allow = bits;
-        if (DBK && tid < 9) {
-            const int nx = rx + tid % 3 - 1, ny = ry + tid / 3 - 1;
-            LfCtu e{0xffffffffu, 0xffff, 0, 0};
-            if (nx >= 0 && ny >= 0 && nx < g.wc && ny < g.hc) {
-                const p265r_ctu& o = ctus[ny * g.wc + nx];
-                e = LfCtu{o.slice_addr, o.tile_id, o.flags, o.deblock_offsets};
-            }
-            s_ctu[tid] = e;
-        }
-    }
-    const int nf_h = (g.h + 7) >> 3;
-    for (int i = tid; i < NB * NB; i += T) {
-        const int bx = (x0 >> 3) - 1 + i % NB, by = (y0 >> 3) - 1 + i / NB;
-        const bool in = bx >= 0 && by >= 0 && bx < g.nf_w && by < nf_h;
-        const size_t o = (size_t)by * g.nf_w + bx;
-        if (DBK) s_map[i] = in ? P->dbk_map[o] : 0;
-        s_nf[i] = in && P->nofilter ? P->nofilter[o] : 0;
-    }
+    lf_fill_maps<uint8_t, NB, DBK, T>(P, w, g, me, s_map, s_nf, s_ctu, &s_allow);
     {
         // sample windows: aligned 16-B (8-B) loads; bytes right of the picture edge come from
         // the row padding (stride >= 64-aligned width) and are never used
@@ -302,34 +375,14 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
     __syncthreads();
 
     if constexpr (DBK) {
-        // slot of the CTU containing luma (x, y) in the 3x3 neighbourhood
-        auto slot = [&](int x, int y) { return ((y >> CTBL) - ry + 1) * 3 + (x >> CTBL) - rx + 1; };
-        auto mblk = [&](int x, int y) { return ((y >> 3) - (y0 >> 3) + 1) * NB + (x >> 3) - (x0 >> 3) + 1; };
-        // filterEdgeFlag for the edge between luma p0 (xp, yp) and q0 (xq, yq); returns Q's offsets or -1
-        auto edge_offs = [&](int xp, int yp, int xq, int yq) -> int {
-            const LfCtu q = s_ctu[slot(xq, yq)];
-            if (!(q.flags & P265R_CTU_DEBLOCK)) return -1;
-            const LfCtu p = s_ctu[slot(xp, yp)];
-            if (!g.lf_tiles && p.tile_id != q.tile_id) return -1;
-            if (p.slice_addr != q.slice_addr && !(q.flags & P265R_CTU_LF_ACROSS_SLICES)) return -1;
-            return q.offs;
-        };
         for (int dir = 0; dir < 2; ++dir) {              // 0: vertical edges, 1: horizontal edges
-            const uint8_t ebit = dir ? DBK_H : DBK_V;
             for (int t = tid; t < SH::N_DBK; t += T) {
                 if (t < SH::NLE * WL) {
                     // ---- luma: edge i, 4-line segment j --------------------------------------------
                     const int i = t / WL, j = t % WL;
-                    const int ge = (dir ? y0 : x0) + 8 * i;            // edge coordinate
-                    const int gs = (dir ? x0 : y0) - 4 + 4 * j;        // segment start
-                    const int xq = dir ? gs : ge, yq = dir ? ge : gs;
-                    const int xp = dir ? xq : xq - 1, yp = dir ? yq - 1 : yq;
-                    if (ge <= 0 || ge >= (dir ? g.h : g.w) || gs < 0 || gs >= (dir ? g.w : g.h)) continue;
-                    const int bq = mblk(xq, yq), bp = mblk(xp, yp);
-                    const int mq = s_map[bq];
-                    if (!(mq & ebit)) continue;
-                    const int offs = edge_offs(xp, yp, xq, yq);
-                    if (offs < 0) continue;
+                    const DbkEdge e = dbk_edge_task<CTBL, uint8_t, NB>(w, g, s_map, s_ctu, dir, 0, i, j);
+                    if (!e.on) continue;
+                    const int bq = e.bq, bp = e.bp, mq = e.mq, offs = e.offs;
                     int Pm[4][4], Qm[4][4];
                     if (!dir) {
 #pragma unroll
@@ -346,8 +399,8 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
                             for (int k = 0; k < 4; ++k) { Pm[a][k] = byte_of(wp, k); Qm[a][k] = byte_of(wq, k); }
                         }
                     }
-                    dbk_luma_seg(Pm, Qm, s_map[bp] & DBK_QP, mq & DBK_QP, nib4(offs & 15), nib4(offs >> 4),
-                                 s_nf[bp] != 0, s_nf[bq] != 0);
+                    dbk_luma_seg<false>(Pm, Qm, s_map[bp] & DBK_QP, mq & DBK_QP, nib4(offs & 15), nib4(offs >> 4),
+                                        s_nf[bp] != 0, s_nf[bq] != 0, 8);
                     if (!dir) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
@@ -372,41 +425,33 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
                     const int u = t - SH::NLE * WL;
                     const int c = u / (SH::NCE * WC), v = u % (SH::NCE * WC);
                     const int i = v / WC, j = v % WC;
-                    const int ge = (dir ? yc0 : xc0) + 8 * i;
-                    const int gs = (dir ? xc0 : yc0) - 4 + 4 * j;
-                    if (ge <= 0 || ge >= (dir ? g.ch : g.cw) || gs < 0 || gs >= (dir ? g.cw : g.ch)) continue;
-                    const int xq = (dir ? gs : ge) << 1, yq = (dir ? ge : gs) << 1;     // luma position of q0
-                    const int xp = dir ? xq : xq - 1, yp = dir ? yq - 1 : yq;
-                    const int bq = mblk(xq, yq), bp = mblk(xp, yp);
-                    const int mq = s_map[bq];
-                    if (!(mq & ebit)) continue;
-                    const int offs = edge_offs(xp, yp, xq, yq);
-                    if (offs < 0) continue;
-                    const int qpi = (((mq & DBK_QP) + (s_map[bp] & DBK_QP) + 1) >> 1) + (c ? g.cqp[1] : g.cqp[0]);
-                    const int tc = c_tc_table[min(max(qpc_table(qpi) + 2 + 2 * nib4(offs >> 4), 0), 53)];
+                    const DbkEdge e = dbk_edge_task<CTBL, uint8_t, NB>(w, g, s_map, s_ctu, dir, 1, i, j);
+                    if (!e.on) continue;
+                    const int bq = e.bq, bp = e.bp;
+                    const int tc = dbk_chroma_tc<false>(s_map[bp] & DBK_QP, e.mq & DBK_QP, c ? g.cqp[1] : g.cqp[0], nib4(e.offs >> 4), 8);
                     const bool nop = s_nf[bp] != 0, noq = s_nf[bq] != 0;
-                    uint32_t* w = s_cw(c);
+                    uint32_t* cwin = s_cw(c);
                     if (!dir) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            uint32_t lo = w[(4 * j + k) * PC + 2 * i], hi = w[(4 * j + k) * PC + 2 * i + 1];
+                            uint32_t lo = cwin[(4 * j + k) * PC + 2 * i], hi = cwin[(4 * j + k) * PC + 2 * i + 1];
                             int p0 = byte_of(lo, 3), q0 = byte_of(hi, 0);
-                            dbk_chroma_line(p0, byte_of(lo, 2), q0, byte_of(hi, 1), tc, nop, noq);
-                            w[(4 * j + k) * PC + 2 * i] = set_byte(lo, 3, p0);
-                            w[(4 * j + k) * PC + 2 * i + 1] = set_byte(hi, 0, q0);
+                            dbk_chroma_line<false>(p0, byte_of(lo, 2), q0, byte_of(hi, 1), tc, nop, noq, 8);
+                            cwin[(4 * j + k) * PC + 2 * i] = set_byte(lo, 3, p0);
+                            cwin[(4 * j + k) * PC + 2 * i + 1] = set_byte(hi, 0, q0);
                         }
                     } else {
-                        const uint32_t w1 = w[(8 * i + 2) * PC + j], w4 = w[(8 * i + 5) * PC + j];
-                        uint32_t w2 = w[(8 * i + 3) * PC + j], w3 = w[(8 * i + 4) * PC + j];
+                        const uint32_t w1 = cwin[(8 * i + 2) * PC + j], w4 = cwin[(8 * i + 5) * PC + j];
+                        uint32_t w2 = cwin[(8 * i + 3) * PC + j], w3 = cwin[(8 * i + 4) * PC + j];
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             int p0 = byte_of(w2, k), q0 = byte_of(w3, k);
-                            dbk_chroma_line(p0, byte_of(w1, k), q0, byte_of(w4, k), tc, nop, noq);
+                            dbk_chroma_line<false>(p0, byte_of(w1, k), q0, byte_of(w4, k), tc, nop, noq, 8);
                             w2 = set_byte(w2, k, p0);
                             w3 = set_byte(w3, k, q0);
                         }
-                        w[(8 * i + 3) * PC + j] = w2;
-                        w[(8 * i + 4) * PC + j] = w3;
+                        cwin[(8 * i + 3) * PC + j] = w2;
+                        cwin[(8 * i + 4) * PC + j] = w3;
                     }
                 }
             }
@@ -442,26 +487,11 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
     for (int q = 0; q < 4; ++q) res[q] = cur[q];
     const int typ = sao_on ? me.sao_type[c] : 0;
     if (typ != 0) {
-        // packed byte arithmetic, 4 samples per dword (SWAR): per sample a table index
-        // (edgeIdx or band slot) is built in a byte, the offsets are looked up 4 at a time
-        // with v_perm_b32 from 8-byte tables, and v + offset is clipped in 16-bit lanes
+        // packed byte arithmetic, 4 samples per dword (the SWAR helpers of sao.h)
         const int cls = me.sao_class[c];
-        int tab[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (typ == 2) {        // raw e = 2 + sgn(v - a) + sgn(v - b): edgeIdx 1, 2, 0, 3, 4
-            tab[0] = me.sao_offset[c][0]; tab[1] = me.sao_offset[c][1];
-            tab[3] = me.sao_offset[c][2]; tab[4] = me.sao_offset[c][3];
-        } else {               // slot 1..4 = bands sao_band_position + 0..3, slot 0 = no offset
-#pragma unroll
-            for (int k = 0; k < 4; ++k) tab[k + 1] = me.sao_offset[c][k];
-        }
-        uint32_t tp_lo = 0, tp_hi = 0, tn_lo = 0, tn_hi = 0;       // max(off, 0) / max(-off, 0)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            tp_lo |= (uint32_t)max(tab[k], 0) << (8 * k);
-            tn_lo |= (uint32_t)max(-tab[k], 0) << (8 * k);
-            tp_hi |= (uint32_t)max(tab[k + 4], 0) << (8 * k);
-            tn_hi |= (uint32_t)max(-tab[k + 4], 0) << (8 * k);
-        }
+        uint32_t o;                                                // SaoOffsetVal[1..4], signed bytes
+        __builtin_memcpy(&o, me.sao_offset[c], 4);
+        const SaoTable tab = sao_table(typ, o);
         // which samples of the unit may be changed: neighbours available (EO), not PCM/bypass
         uint32_t okm[4];
         const bool has_l = X > 0, has_u = Y > 0, has_d = Y + 1 < H, right_in = X + U < W;
@@ -497,27 +527,12 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
             if (s_nf[((ly >> 3) - (y0 >> 3) + 1) * NB + (lx >> 3) - (x0 >> 3) + 1]) m = 0;
             okm[q] = m;
         }
-        auto split_lo = [](uint32_t v) { return __builtin_amdgcn_perm(0u, v, 0x0c020c00u); };   // bytes 0, 2
-        auto split_hi = [](uint32_t v) { return __builtin_amdgcn_perm(0u, v, 0x0c030c01u); };   // bytes 1, 3
-        auto join = [](uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x06020400u); };
-        // v + table[sel] clipped to [0, 255], 4 samples
-        auto apply = [&](uint32_t v, uint32_t sel) {
-            const uint32_t pos = __builtin_amdgcn_perm(tp_hi, tp_lo, sel);
-            const uint32_t neg = __builtin_amdgcn_perm(tn_hi, tn_lo, sel);
-            const uint32_t m255 = 0x00ff00ffu;
-            const uint32_t rl = pk_min_u16(pk_subsat_u16(pk_add_u16(split_lo(v), split_lo(pos)), split_lo(neg)), m255);
-            const uint32_t rh = pk_min_u16(pk_subsat_u16(pk_add_u16(split_hi(v), split_hi(pos)), split_hi(neg)), m255);
-            return join(rl, rh);
-        };
         if (typ == 1) {
-            const uint32_t badd = (uint32_t)((32 - cls) & 31) * 0x01010101u;
+            const uint32_t badd = sao_band_add(cls);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (q >= NW) break;
-                const uint32_t k = (((cur[q] >> 3) & 0x1f1f1f1fu) + badd) & 0x1f1f1f1fu;
-                const uint32_t big = (((k & 0x1c1c1c1cu) + 0x7f7f7f7fu) & 0x80808080u) >> 7;
-                const uint32_t sel = (k + 0x01010101u) & ~((big << 8) - big);
-                res[q] = (apply(cur[q], sel) & okm[q]) | (cur[q] & ~okm[q]);
+                res[q] = (sao_apply(tab, cur[q], sao_band_sel(cur[q], badd)) & okm[q]) | (cur[q] & ~okm[q]);
             }
         } else {
             // rows above / below with one dword either side (window dwords wd-1 .. wd+NW)
@@ -529,11 +544,6 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
                 up[q] = in ? win[(wr - 1) * wst + wd - 1 + q] : 0u;
                 dn[q] = in ? win[(wr + 1) * wst + wd - 1 + q] : 0u;
             }
-            // 2 + sgn(v - a) + sgn(v - b) in unsigned 16-bit lanes: [v > a] = min(sat(v - a), 1)
-            auto gt = [&](uint32_t v, uint32_t a) { return pk_min_u16(pk_subsat_u16(v, a), 0x00010001u); };
-            auto edge = [&](uint32_t v, uint32_t a, uint32_t b) {
-                return pk_sub_u16(pk_add_u16(pk_add_u16(gt(v, a), gt(v, b)), 0x00020002u), pk_add_u16(gt(a, v), gt(b, v)));
-            };
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (q >= NW) break;
@@ -543,8 +553,7 @@ __global__ __launch_bounds__(LfShape<CTBL>::threads(DBK)) void loopfilter_kernel
                 else if (cls == 2) { a = __builtin_amdgcn_alignbyte(up[q + 1], up[q], 3); b = __builtin_amdgcn_alignbyte(dn[q + 2], dn[q + 1], 1); }
                 else { a = __builtin_amdgcn_alignbyte(up[q + 2], up[q + 1], 1); b = __builtin_amdgcn_alignbyte(dn[q + 1], dn[q], 3); }
                 const uint32_t v = cur[q];
-                const uint32_t sel = join(edge(split_lo(v), split_lo(a), split_lo(b)), edge(split_hi(v), split_hi(a), split_hi(b)));
-                res[q] = (apply(v, sel) & okm[q]) | (v & ~okm[q]);
+                res[q] = (sao_apply(tab, v, sao_edge_sel(v, a, b)) & okm[q]) | (v & ~okm[q]);
             }
         }
     }

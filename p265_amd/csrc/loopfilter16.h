@@ -11,6 +11,8 @@
 // uint16 samples (luma (S+8)^2, chroma (S/2+8)^2 each), deblocked there (the window is closed under
 // deblocking, loopfilter.h), and SAO of the CTB runs from it, one sample per thread and step.  Plain
 // per-sample arithmetic: this path is for correctness and coverage of Main 10, not the headline.
+// The filters (dbk_luma_seg<true>, dbk_chroma_line<true>), the window prologue, the map fill and the
+// edge-task decode are the ones of loopfilter.h; the LDS layout, sample access and SAO stage are this file's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,56 +22,6 @@
 #include "sao.h"
 
 namespace p265r {
-
-__device__ __forceinline__ void dbk_luma_seg16(int (&P)[4][4], int (&Q)[4][4], int qpp, int qpq, int boff, int toff,
-                                               bool nop, bool noq, int bd) {
-    const int qpl = (qpq + qpp + 1) >> 1;
-    const int beta = dbk_beta(min(max(qpl + 2 * boff, 0), 51)) << (bd - 8);
-    const int tc = (int)c_tc_table[min(max(qpl + 2 + 2 * toff, 0), 53)] << (bd - 8);     // bS = 2
-    const int maxv = (1 << bd) - 1;
-    const int dp0 = abs(P[2][0] - 2 * P[1][0] + P[0][0]), dp3 = abs(P[2][3] - 2 * P[1][3] + P[0][3]);
-    const int dq0 = abs(Q[2][0] - 2 * Q[1][0] + Q[0][0]), dq3 = abs(Q[2][3] - 2 * Q[1][3] + Q[0][3]);
-    if (dp0 + dq0 + dp3 + dq3 >= beta) return;
-    auto dsam = [&](int k, int dpq) {
-        return dpq < (beta >> 2) && abs(P[3][k] - P[0][k]) + abs(Q[0][k] - Q[3][k]) < (beta >> 3) &&
-               abs(P[0][k] - Q[0][k]) < ((5 * tc + 1) >> 1);
-    };
-    const bool strong = dsam(0, 2 * (dp0 + dq0)) && dsam(3, 2 * (dp3 + dq3));
-    const int side = (beta + (beta >> 1)) >> 3;
-    const bool dep = dp0 + dp3 < side, deq = dq0 + dq3 < side;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int p0 = P[0][k], p1 = P[1][k], p2 = P[2][k], p3 = P[3][k];
-        const int q0 = Q[0][k], q1 = Q[1][k], q2 = Q[2][k], q3 = Q[3][k];
-        if (strong) {
-            const int t2 = 2 * tc;
-            if (!nop) {
-                P[0][k] = min(max((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3, p0 - t2), p0 + t2);
-                P[1][k] = min(max((p2 + p1 + p0 + q0 + 2) >> 2, p1 - t2), p1 + t2);
-                P[2][k] = min(max((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3, p2 - t2), p2 + t2);
-            }
-            if (!noq) {
-                Q[0][k] = min(max((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3, q0 - t2), q0 + t2);
-                Q[1][k] = min(max((p0 + q0 + q1 + q2 + 2) >> 2, q1 - t2), q1 + t2);
-                Q[2][k] = min(max((p0 + q0 + q1 + 3 * q2 + 2 * q3 + 4) >> 3, q2 - t2), q2 + t2);
-            }
-        } else {
-            int d = (9 * (q0 - p0) - 3 * (q1 - p1) + 8) >> 4;
-            if (abs(d) < tc * 10) {
-                d = min(max(d, -tc), tc);
-                const int th = tc >> 1;
-                if (!nop) {
-                    P[0][k] = min(max(p0 + d, 0), maxv);
-                    if (dep) P[1][k] = min(max(p1 + min(max((((p2 + p0 + 1) >> 1) - p1 + d) >> 1, -th), th), 0), maxv);
-                }
-                if (!noq) {
-                    Q[0][k] = min(max(q0 - d, 0), maxv);
-                    if (deq) Q[1][k] = min(max(q1 + min(max((((q2 + q0 + 1) >> 1) - q1 - d) >> 1, -th), th), 0), maxv);
-                }
-            }
-        }
-    }
-}
 
 // grid (8 * ceil(CTUs * pictures / 8)), 256 threads; planes of uint16_t samples, Geo::stride samples
 template <int CTBL, bool DBK>
@@ -87,46 +39,15 @@ __global__ __launch_bounds__(256) void loopfilter16_kernel(const DevPic* __restr
     __shared__ LfCtu s_ctu[9];
     __shared__ uint32_t s_allow;
 
-    const int n_ctus = g.wc * g.hc;
-    const int unit = xcd_unit(blockIdx.x, n_ctus * n_pics);
-    if (unit >= n_ctus * n_pics) return;                     // whole workgroup: before any barrier
-    const int pic = unit / n_ctus;
-    int rs = unit - pic * n_ctus;
-    const DevPic* P = pics + pic;
-    const p265r_ctu* ctus = P->ctus;
-    const int rx = rs % g.wc, ry = rs / g.wc;
-    if (P265R_RAGGED && g.ragged) {
-        g = pic_geo(g, (uint32_t)__builtin_amdgcn_readfirstlane((int)P->wh));
-        if (rx >= g.wc || ry >= g.hc) return;
-        rs = ry * g.wc + rx;
-    }
-    const int x0 = rx * S, y0 = ry * S, xc0 = x0 >> 1, yc0 = y0 >> 1;
+    const LfWindow w = lf_window<CTBL>(pics, g, n_pics);     // (g: this picture's from here on)
+    if (w.outside) return;                                   // whole workgroup: before any barrier
+    const DevPic* P = pics + w.pic;
+    const int x0 = w.x0, y0 = w.y0, xc0 = x0 >> 1, yc0 = y0 >> 1;
     const int tid = threadIdx.x;
-    const p265r_ctu me = ctus[rs];
+    const p265r_ctu me = P->ctus[w.rs];
     const int qp_off = 6 * (g.bd[0] - 8);                    // QpBdOffsetY: the map holds Qp'Y
 
-    if (tid < 64) {
-        const bool ok = tid < 9 && sao_allow(ctus, me, rs, rx, ry, tid % 3 - 1, tid / 3 - 1, g);
-        const uint32_t bits = (uint32_t)__ballot(ok);
-        if (tid == 0) s_allow = bits;
-        if (DBK && tid < 9) {
-            const int nx = rx + tid % 3 - 1, ny = ry + tid / 3 - 1;
-            LfCtu e{0xffffffffu, 0xffff, 0, 0};
-            if (nx >= 0 && ny >= 0 && nx < g.wc && ny < g.hc) {
-                const p265r_ctu& o = ctus[ny * g.wc + nx];
-                e = LfCtu{o.slice_addr, o.tile_id, o.flags, o.deblock_offsets};
-            }
-            s_ctu[tid] = e;
-        }
-    }
-    const int nf_h = (g.h + 7) >> 3;
-    for (int i = tid; i < NB * NB; i += T) {
-        const int bx = (x0 >> 3) - 1 + i % NB, by = (y0 >> 3) - 1 + i / NB;
-        const bool in = bx >= 0 && by >= 0 && bx < g.nf_w && by < nf_h;
-        const size_t o = (size_t)by * g.nf_w + bx;
-        if (DBK) s_map[i] = in ? reinterpret_cast<const uint16_t*>(P->dbk_map)[o] : 0;
-        s_nf[i] = in && P->nofilter ? P->nofilter[o] : 0;
-    }
+    lf_fill_maps<uint16_t, NB, DBK, T>(P, w, g, me, s_map, s_nf, s_ctu, &s_allow);
     {
         const uint16_t* src = reinterpret_cast<const uint16_t*>(P->rec[0]);
         for (int i = tid; i < RL * RL; i += T) {
@@ -145,31 +66,14 @@ __global__ __launch_bounds__(256) void loopfilter16_kernel(const DevPic* __restr
     __syncthreads();
 
     if constexpr (DBK) {
-        auto slot = [&](int x, int y) { return ((y >> CTBL) - ry + 1) * 3 + (x >> CTBL) - rx + 1; };
-        auto mblk = [&](int x, int y) { return ((y >> 3) - (y0 >> 3) + 1) * NB + (x >> 3) - (x0 >> 3) + 1; };
-        auto edge_offs = [&](int xp, int yp, int xq, int yq) -> int {
-            const LfCtu q = s_ctu[slot(xq, yq)];
-            if (!(q.flags & P265R_CTU_DEBLOCK)) return -1;
-            const LfCtu p = s_ctu[slot(xp, yp)];
-            if (!g.lf_tiles && p.tile_id != q.tile_id) return -1;
-            if (p.slice_addr != q.slice_addr && !(q.flags & P265R_CTU_LF_ACROSS_SLICES)) return -1;
-            return q.offs;
-        };
         constexpr int N_DBK = NLE * WL + 2 * NCE * WC;
         for (int dir = 0; dir < 2; ++dir) {                  // 0: vertical edges, 1: horizontal edges
-            const int ebit = dir ? DBK16_H : DBK16_V;
             for (int t = tid; t < N_DBK; t += T) {
                 if (t < NLE * WL) {
                     const int i = t / WL, j = t % WL;
-                    const int ge = (dir ? y0 : x0) + 8 * i, gs = (dir ? x0 : y0) - 4 + 4 * j;
-                    const int xq = dir ? gs : ge, yq = dir ? ge : gs;
-                    const int xp = dir ? xq : xq - 1, yp = dir ? yq - 1 : yq;
-                    if (ge <= 0 || ge >= (dir ? g.h : g.w) || gs < 0 || gs >= (dir ? g.w : g.h)) continue;
-                    const int bq = mblk(xq, yq), bp = mblk(xp, yp);
-                    const int mq = s_map[bq];
-                    if (!(mq & ebit)) continue;
-                    const int offs = edge_offs(xp, yp, xq, yq);
-                    if (offs < 0) continue;
+                    const DbkEdge ed = dbk_edge_task<CTBL, uint16_t, NB>(w, g, s_map, s_ctu, dir, 0, i, j);
+                    if (!ed.on) continue;
+                    const int bq = ed.bq, bp = ed.bp, mq = ed.mq, offs = ed.offs;
                     // window sample of P_a / Q_a on line k
                     auto at = [&](int a, int k, bool q) -> uint16_t& {
                         const int e = 8 * i + (q ? 4 + a : 3 - a), l = 4 * j + k;
@@ -180,8 +84,8 @@ __global__ __launch_bounds__(256) void loopfilter16_kernel(const DevPic* __restr
                     for (int a = 0; a < 4; ++a)
 #pragma unroll
                         for (int k = 0; k < 4; ++k) { Pm[a][k] = at(a, k, false); Qm[a][k] = at(a, k, true); }
-                    dbk_luma_seg16(Pm, Qm, (s_map[bp] & DBK16_QP) - qp_off, (mq & DBK16_QP) - qp_off, nib4(offs & 15),
-                                   nib4(offs >> 4), s_nf[bp] != 0, s_nf[bq] != 0, g.bd[0]);
+                    dbk_luma_seg<true>(Pm, Qm, (s_map[bp] & DBK16_QP) - qp_off, (mq & DBK16_QP) - qp_off, nib4(offs & 15),
+                                       nib4(offs >> 4), s_nf[bp] != 0, s_nf[bq] != 0, g.bd[0]);
 #pragma unroll
                     for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -190,32 +94,24 @@ __global__ __launch_bounds__(256) void loopfilter16_kernel(const DevPic* __restr
                     const int u = t - NLE * WL;
                     const int c = u / (NCE * WC), v = u % (NCE * WC);
                     const int i = v / WC, j = v % WC;
-                    const int ge = (dir ? yc0 : xc0) + 8 * i, gs = (dir ? xc0 : yc0) - 4 + 4 * j;
-                    if (ge <= 0 || ge >= (dir ? g.ch : g.cw) || gs < 0 || gs >= (dir ? g.cw : g.ch)) continue;
-                    const int xq = (dir ? gs : ge) << 1, yq = (dir ? ge : gs) << 1;
-                    const int xp = dir ? xq : xq - 1, yp = dir ? yq - 1 : yq;
-                    const int bq = mblk(xq, yq), bp = mblk(xp, yp);
-                    const int mq = s_map[bq];
-                    if (!(mq & ebit)) continue;
-                    const int offs = edge_offs(xp, yp, xq, yq);
-                    if (offs < 0) continue;
-                    const int qpi = ((((mq & DBK16_QP) - qp_off) + ((s_map[bp] & DBK16_QP) - qp_off) + 1) >> 1) +
-                                    (c ? g.cqp[1] : g.cqp[0]);
-                    const int tc = (int)c_tc_table[min(max(qpc_table(qpi) + 2 + 2 * nib4(offs >> 4), 0), 53)] << (g.bd[1] - 8);
-                    const int maxc = (1 << g.bd[1]) - 1;
+                    const DbkEdge e = dbk_edge_task<CTBL, uint16_t, NB>(w, g, s_map, s_ctu, dir, 1, i, j);
+                    if (!e.on) continue;
+                    const int bq = e.bq, bp = e.bp;
+                    const int tc = dbk_chroma_tc<true>((s_map[bp] & DBK16_QP) - qp_off, (e.mq & DBK16_QP) - qp_off,
+                                                       c ? g.cqp[1] : g.cqp[0], nib4(e.offs >> 4), g.bd[1]);
                     const bool nop = s_nf[bp] != 0, noq = s_nf[bq] != 0;
-                    uint16_t* w = s_c[c];
+                    uint16_t* win = s_c[c];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const int l = 4 * j + k, e = 8 * i;
-                        uint16_t& p0 = dir ? w[(e + 3) * RC + l] : w[l * RC + e + 3];
-                        uint16_t& q0 = dir ? w[(e + 4) * RC + l] : w[l * RC + e + 4];
-                        const int p1 = dir ? w[(e + 2) * RC + l] : w[l * RC + e + 2];
-                        const int q1 = dir ? w[(e + 5) * RC + l] : w[l * RC + e + 5];
-                        const int d = min(max((((int)q0 - (int)p0) * 4 + p1 - q1 + 4) >> 3, -tc), tc);
-                        const int np0 = min(max((int)p0 + d, 0), maxc), nq0 = min(max((int)q0 - d, 0), maxc);
-                        if (!nop) p0 = (uint16_t)np0;
-                        if (!noq) q0 = (uint16_t)nq0;
+                        const int l = 4 * j + k, eo = 8 * i;
+                        uint16_t& rp0 = dir ? win[(eo + 3) * RC + l] : win[l * RC + eo + 3];
+                        uint16_t& rq0 = dir ? win[(eo + 4) * RC + l] : win[l * RC + eo + 4];
+                        const int p1 = dir ? win[(eo + 2) * RC + l] : win[l * RC + eo + 2];
+                        const int q1 = dir ? win[(eo + 5) * RC + l] : win[l * RC + eo + 5];
+                        int p0 = rp0, q0 = rq0;
+                        dbk_chroma_line<true>(p0, p1, q0, q1, tc, nop, noq, g.bd[1]);
+                        if (!nop) rp0 = (uint16_t)p0;
+                        if (!noq) rq0 = (uint16_t)q0;
                     }
                 }
             }

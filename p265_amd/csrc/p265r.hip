@@ -511,6 +511,63 @@ int launch_rows(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
     return w == 12 ? launch_rows_w<12, 6>(ctx, b, st, alone) : launch_rows_w<8, 6>(ctx, b, st, alone);
 }
 
+// grid of a strip kernel (sao.h strip_pos): one wave per unit, 4 waves per block, the block count
+// rounded up to the 8 XCDs
+int strip_grid(int units_per_pic, int n_pics, unsigned* blocks) {
+    const long long waves = (long long)units_per_pic * n_pics;
+    if (waves >= (1ll << 31) - 64) return P265R_ERANGE;
+    *blocks = (unsigned)(((waves + 3) / 4 + 7) / 8 * 8);
+    return P265R_OK;
+}
+
+// The in-loop filter pass of a batch (deblocking + SAO) on stream s; `launched` counts the kernel.
+//   SAO only, 16-bit samples: sao16.h, 8 samples per lane, 496-sample strips
+//   SAO only, CTB 32 / 64: sao_strip16.h, 16 samples per lane, 992-sample strips; it filters 2-row chunks
+//     and takes plane heights in multiples of 4 (luma a multiple of MinCbSizeY >= 8 in a conforming
+//     stream; anything else goes to the 4-B strip kernel)
+//   SAO only, CTB 16 (or P265R_SAO_ROWS=2): sao_rows.h, 4 samples per lane, 248-sample strips
+//   with deblocking (or P265R_SAO_ROWS=0): the window kernels, loopfilter.h / loopfilter16.h
+// Strip kernels: one wave per (picture, CTB row, component, strip), 4 waves per block; window kernels:
+// one workgroup per (picture, CTB).
+int launch_loop_filters(p265r_ctx* ctx, p265r_batch* b, const Geo& g, hipStream_t s, int* launched) {
+    if (!b->dbk && !b->sao) return P265R_OK;
+    const bool sao_only = b->sao && !b->dbk;
+    const int np = b->n_pics;
+    unsigned blocks = 0;
+    if (sao_only && g.pel16) {
+        if (int rc = strip_grid(strip_units(g, strip_samples(8)), np, &blocks)) return rc;
+        sao16_strip_kernel<<<blocks, 256, 0, s>>>(b->d_pics, g, b->view, np);
+    } else if (sao_only && !g.pel16 && ctx->sao_rows == 1 && g.ctb_log2 >= 5 && g.h % 8 == 0) {
+        if (int rc = strip_grid(strip_units(g, strip_samples(16)), np, &blocks)) return rc;
+        if (g.ctb_log2 == 6) sao_strip16_kernel<6><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, np);
+        else sao_strip16_kernel<5><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, np);
+    } else if (sao_only && !g.pel16 && ctx->sao_rows) {
+        if (int rc = strip_grid(strip_units(g, strip_samples(4)), np, &blocks)) return rc;
+        sao_rows_kernel<<<blocks, 256, 0, s>>>(b->d_pics, g, np);
+    } else {
+        const long long units = (long long)ctx->n_ctus * np;
+        if (units >= (1ll << 31) - 8) return P265R_ERANGE;
+        blocks = (unsigned)((units + 7) / 8 * 8);
+        const int so = b->sao ? 1 : 0;
+        auto window = [&](auto ctbl, auto dbk) {
+            constexpr int L = decltype(ctbl)::value;
+            constexpr bool D = decltype(dbk)::value;
+            if (g.pel16) loopfilter16_kernel<L, D><<<blocks, 256, 0, s>>>(b->d_pics, g, so, np);
+            else loopfilter_kernel<L, D><<<blocks, LfShape<L>::threads(D), 0, s>>>(b->d_pics, g, so, np);
+        };
+        auto by_dbk = [&](auto ctbl) {
+            if (b->dbk) window(ctbl, std::true_type{});
+            else window(ctbl, std::false_type{});
+        };
+        if (g.ctb_log2 == 6) by_dbk(std::integral_constant<int, 6>{});
+        else if (g.ctb_log2 == 5) by_dbk(std::integral_constant<int, 5>{});
+        else by_dbk(std::integral_constant<int, 4>{});
+    }
+    ++*launched;
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1431,67 +1488,9 @@ int p265r_batch_run(p265r_ctx* ctx, p265r_batch* b) {
         s = ctx->aux[li];
         HIP_TRY(hipStreamWaitEvent(s, b->intra_done, 0));
     }
-    if (g.pel16 && b->sao && !b->dbk && !(skip & 4)) {
-        // 16-bit samples, SAO only: the strip kernel (sao16.h), 8 samples per lane, one wave per (picture,
-        // CTB row, component, 496-sample strip), 4 waves per block, blocks dealt XCD-aware
-        const long long waves = (long long)sao16b_units(g) * b->n_pics;
-        if (waves >= (1ll << 31) - 64) return P265R_ERANGE;
-        const unsigned blocks = (unsigned)((waves + 3) / 4 + 7) / 8 * 8;
-        sao16_strip_kernel<<<blocks, 256, 0, s>>>(b->d_pics, g, b->view, b->n_pics);
-        ++tm.sao_launches;
-        HIP_TRY(hipGetLastError());
-    } else if (g.pel16 && (b->dbk || b->sao) && !(skip & 4)) {
-        // 16-bit samples (Main 10): deblocking + SAO in loopfilter16.h, with or without deblocking
-        const long long units = (long long)ctx->n_ctus * b->n_pics;
-        if (units >= (1ll << 31) - 8) return P265R_ERANGE;
-        const dim3 grid((unsigned)((units + 7) / 8 * 8));
-        const int so = b->sao ? 1 : 0, np = b->n_pics;
-        switch (g.ctb_log2 * 2 + (b->dbk ? 1 : 0)) {
-            case 12: loopfilter16_kernel<6, false><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-            case 13: loopfilter16_kernel<6, true><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-            case 10: loopfilter16_kernel<5, false><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-            case 11: loopfilter16_kernel<5, true><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-            case 8: loopfilter16_kernel<4, false><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-            default: loopfilter16_kernel<4, true><<<grid, 256, 0, s>>>(b->d_pics, g, so, np); break;
-        }
-        ++tm.sao_launches;
-        HIP_TRY(hipGetLastError());
-    } else if (b->sao && !b->dbk && ctx->sao_rows == 1 && g.ctb_log2 >= 5 && g.h % 8 == 0 && !(skip & 4)) {
-        // SAO only, CTB 32 / 64: the 16-samples-per-lane strip kernel (sao_strip16.h), one wave per
-        // (picture, CTB row, component, 992-sample strip), 4 waves per block, blocks dealt XCD-aware;
-        // it filters 4-row chunks and takes plane heights in multiples of 4 (luma a multiple of
-        // MinCbSizeY >= 8 in a conforming stream; anything else goes to the 4-B strip kernel)
-        const long long waves = (long long)sao16_units(g) * b->n_pics;
-        if (waves >= (1ll << 31) - 64) return P265R_ERANGE;
-        const unsigned blocks = (unsigned)((waves + 3) / 4 + 7) / 8 * 8;
-        if (g.ctb_log2 == 6) sao_strip16_kernel<6><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, b->n_pics);
-        else sao_strip16_kernel<5><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, b->n_pics);
-        ++tm.sao_launches;
-        HIP_TRY(hipGetLastError());
-    } else if (b->sao && !b->dbk && ctx->sao_rows && !(skip & 4)) {
-        // SAO only, CTB 16 (or P265R_SAO_ROWS=2): the strip kernel (sao_rows.h), one wave per
-        // (picture, component, CTB row, 248-sample strip), 4 waves per block, blocks dealt XCD-aware
-        const long long waves = (long long)sao_rows_units(g) * b->n_pics;
-        if (waves >= (1ll << 31) - 64) return P265R_ERANGE;
-        const long long blocks = (waves + 3) / 4;
-        sao_rows_kernel<<<(unsigned)((blocks + 7) / 8 * 8), 256, 0, s>>>(b->d_pics, g, b->n_pics);
-        ++tm.sao_launches;
-        HIP_TRY(hipGetLastError());
-    } else if ((b->dbk || b->sao) && !(skip & 4)) {
-        const long long units = (long long)ctx->n_ctus * b->n_pics;
-        if (units >= (1ll << 31) - 8) return P265R_ERANGE;
-        const dim3 grid((unsigned)((units + 7) / 8 * 8));
-        const int so = b->sao ? 1 : 0, np = b->n_pics;
-        switch (g.ctb_log2 * 2 + (b->dbk ? 1 : 0)) {
-            case 12: loopfilter_kernel<6, false><<<grid, LfShape<6>::threads(false), 0, s>>>(b->d_pics, g, so, np); break;
-            case 13: loopfilter_kernel<6, true><<<grid, LfShape<6>::threads(true), 0, s>>>(b->d_pics, g, so, np); break;
-            case 10: loopfilter_kernel<5, false><<<grid, LfShape<5>::threads(false), 0, s>>>(b->d_pics, g, so, np); break;
-            case 11: loopfilter_kernel<5, true><<<grid, LfShape<5>::threads(true), 0, s>>>(b->d_pics, g, so, np); break;
-            case 8: loopfilter_kernel<4, false><<<grid, LfShape<4>::threads(false), 0, s>>>(b->d_pics, g, so, np); break;
-            default: loopfilter_kernel<4, true><<<grid, LfShape<4>::threads(true), 0, s>>>(b->d_pics, g, so, np); break;
-        }
-        ++tm.sao_launches;
-        HIP_TRY(hipGetLastError());
+    if (!(skip & 4)) {
+        int rc = launch_loop_filters(ctx, b, g, s, &tm.sao_launches);
+        if (rc) return rc;
     }
     if (sao_aux) {
         HIP_TRY(hipEventRecord(b->sao_done, s));

@@ -671,6 +671,29 @@ def test_sao_only_window_kernel(recon_mod, kernel, monkeypatch):
         _check_c(recon_mod, params, pics, "sao-only")
 
 
+@pytest.mark.parametrize("bd,w,h,ctb_log2", [(8, 2000, 72, 6), (8, 2000, 72, 5), (10, 1000, 72, 5), (10, 1000, 136, 6)])
+def test_sao_strip_second_strips(recon_mod, bd, w, h, ctb_log2):
+    """SAO-only batches whose planes reach into a second strip of the streaming strip kernels: at 8 bits
+    chroma width 1000 (sao_strip16.h, 992-sample strips: one 8-sample column past the strip, a partial
+    16-sample lane), at 10 bits luma width 1000 and chroma width 500 (sao16.h, 496-sample strips: 4 samples
+    past the strip, a partial 8-sample lane).  Tiles without filtering across them and slices put different
+    3x3 permissions on either side of the strip boundary.  SAO must change samples of every component in
+    the second strip, or the comparison there would say nothing."""
+    params = R.make_params(pic_width=w, pic_height=h, ctb_log2_size=ctb_log2, loop_filter_across_tiles=0,
+                           bit_depth_luma=bd, bit_depth_chroma=bd)
+    pic = synth.make_picture(params, 7000 + bd + ctb_log2, perf=False, tiles=(3, 2), n_slices=4, lf_across_slices=None,
+                             deblocking=False, pcm_rate=0.03, bypass_rate=0.03)
+    with recon_mod.ReconContext(params) as ctx:
+        outs, recs = ctx.decode([pic], with_recon=True)
+    rec_ref, out_ref = O.decode_picture(R.params_dict(params), pic.as_oracle_dict())
+    strip = 992 if bd == 8 else 496
+    for c in range(3):
+        changed = int(np.count_nonzero(np.asarray(rec_ref[c])[:, strip:] != np.asarray(out_ref[c])[:, strip:]))
+        assert changed > 0, "oracle: SAO changes no sample at x >= %d of component %d" % (strip, c)
+        np.testing.assert_array_equal(recs[0][c], rec_ref[c], err_msg="strip2 recon c%d" % c)
+        np.testing.assert_array_equal(outs[0][c], out_ref[c], err_msg="strip2 sao c%d" % c)
+
+
 # ---------------------------------------------------------------------------------
 # C5 with loop_filter_across_tiles_enabled_flag = 1: tile reconstruction + halo + filtering
 # ---------------------------------------------------------------------------------
