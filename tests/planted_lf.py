@@ -35,24 +35,30 @@ CTB_LOG2 = (4, 5, 6)
 OFFSETS = ((0, 0), (-6, -6), (6, 6), (-6, 6), (6, -6), (2, -3), (-1, 4), (0, -1))     # (beta, tc) _offset_div2
 
 
-def params_of(bit_depth, ctb_log2, variant, sao=False):
+def params_of(bit_depth, ctb_log2, variant, sao=False, w=W, h=H):
     v = VARIANTS[variant]
-    return R.make_params(pic_width=W, pic_height=H, ctb_log2_size=ctb_log2, sample_adaptive_offset=int(sao),
+    return R.make_params(pic_width=w, pic_height=h, ctb_log2_size=ctb_log2, sample_adaptive_offset=int(sao),
                          bit_depth_luma=bit_depth, bit_depth_chroma=bit_depth, loop_filter_across_tiles=v["lf_tiles"],
                          pps_cb_qp_offset=v["cb"], pps_cr_qp_offset=v["cr"])
 
 
 class Spec:
     """What a picture is built from: the CU size, QpY and the bypass flag per CU ([cy][cx]), and per CTU
-    (raster) slice id, tile id, slice_loop_filter_across_slices, deblocking on, (beta, tc) offsets."""
+    (raster) slice id, tile id, slice_loop_filter_across_slices, deblocking on, (beta, tc) offsets.  The
+    picture is 128 x 128 unless ``w`` and ``h`` say otherwise (multiples of 8; CTBs and CUs at the right and
+    bottom may be partial).  ``nf_pcm``: PCM CUs under pcm_loop_filter_disabled (a no-filter CU without
+    bypass); ``sao``: per CTU the SAO arguments of PictureBuilder.add_ctu, or None."""
 
-    def __init__(self, bit_depth, ctb_log2, cu):
+    def __init__(self, bit_depth, ctb_log2, cu, w=W, h=H):
         self.bd, self.ctb_log2, self.cu = bit_depth, ctb_log2, cu
+        self.w, self.h = w, h
         self.ctb = 1 << ctb_log2
-        self.wc = W >> ctb_log2
-        n, nc = W // cu, self.wc * self.wc
-        self.qp = np.full((n, n), 30, np.int64)
-        self.nf = np.zeros((n, n), bool)
+        self.wc, self.hc = -(-w >> ctb_log2), -(-h >> ctb_log2)
+        n, nc = (-(-h // cu), -(-w // cu)), self.wc * self.hc
+        self.qp = np.full(n, 30, np.int64)
+        self.nf = np.zeros(n, bool)
+        self.nf_pcm = np.zeros(n, bool)
+        self.sao = None
         self.slice = np.zeros(nc, np.int64)
         self.tile = np.zeros(nc, np.int64)
         self.lf_across = np.ones(nc, bool)
@@ -263,10 +269,12 @@ def _sao_args(bit_depth, rs):
     return dict(sao_type=(2, 2, 2), sao_abs=[[a] * 4] * 3, sao_eo=(rs % 4, (rs + 1) % 4, (rs + 1) % 4))
 
 
-def build(spec, planes, variant, sao=False, meta=None, nxn_modes=None):
+def build(spec, planes, variant, sao=False, meta=None, nxn_modes=None, params=None):
     """-> records.Picture of PCM CUs carrying ``planes`` (``nxn_modes``: ordinary 8 x 8 NxN CUs without a
-    DC residual instead, which predict their own samples)."""
-    params = params_of(spec.bd, spec.ctb_log2, variant, sao)
+    DC residual instead, which predict their own samples).  ``sao``: the SAO twin's arguments for every CTU,
+    unless spec.sao gives each CTU its own; ``params``: instead of params_of(variant)."""
+    if params is None:
+        params = params_of(spec.bd, spec.ctb_log2, variant, sao, spec.w, spec.h)
     offy, offc = R.qp_bd_offset(params, 0), R.qp_bd_offset(params, 1)
     b = frontend.PictureBuilder(params)
     cu_log2 = spec.cu.bit_length() - 1
@@ -274,6 +282,8 @@ def build(spec, planes, variant, sao=False, meta=None, nxn_modes=None):
 
     def node(x, y, log2):
         n = 1 << log2
+        if x >= spec.w or y >= spec.h:
+            return
         if log2 > cu_log2:
             for i in range(4):
                 node(x + (n >> 1) * (i % 2), y + (n >> 1) * (i // 2), log2 - 1)
@@ -290,18 +300,19 @@ def build(spec, planes, variant, sao=False, meta=None, nxn_modes=None):
             return
         smp = [planes[c][y >> (c > 0):(y + n) >> (c > 0), x >> (c > 0):(x + n) >> (c > 0)].astype(np.int16)
                for c in range(3)]
+        b.pcm_lf_disabled = bool(spec.nf_pcm[y // n, x // n])
         b.add_cu(x, y, log2, 0, [0] * 4, 0, *qps, [], pcm=True, pcm_samples=smp, bypass=bool(spec.nf[y // n, x // n]))
 
     first = {}
     order = np.lexsort((np.arange(len(spec.tile)), spec.tile))        # tile scan: a slice's address is its first CTU
     for rs in order:
         first.setdefault((int(spec.tile[rs]), int(spec.slice[rs])), int(rs))
-    for rs in range(spec.wc * spec.wc):
+    for rs in range(spec.wc * spec.hc):
         node((rs % spec.wc) << spec.ctb_log2, (rs // spec.wc) << spec.ctb_log2, spec.ctb_log2)
         bo, to = spec.off[rs]
         b.add_ctu(rs, slice_addr=first[(int(spec.tile[rs]), int(spec.slice[rs]))], tile_id=int(spec.tile[rs]),
                   lf_across_slices=bool(spec.lf_across[rs]), deblocking=bool(spec.dbk[rs]), beta_offset_div2=bo,
-                  tc_offset_div2=to, **(_sao_args(spec.bd, rs) if sao else {}))
+                  tc_offset_div2=to, **(spec.sao[rs] if spec.sao is not None else _sao_args(spec.bd, rs) if sao else {}))
     m = dict(bit_depth=spec.bd, ctb_log2=spec.ctb_log2, cu=spec.cu, variant=variant, sao=bool(sao))
     m.update(meta or {})
     pic = b.finish(meta=m)
