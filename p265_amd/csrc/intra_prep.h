@@ -134,7 +134,7 @@ struct ChromaJobLds { uint32_t w0, w2, w3, w4, w5; };
 
 // the four jobs at slots s..s+3 are fast Cb+Cr 4x4 pairs of one 8x8 chroma region, in z-order,
 // and their eight residuals are addressable as base + 16 * code (code <= 14; 15 = zero block):
-// coded chroma 4x4 TBs of one class are packed in decode order at upload (p265r.hip), so the
+// coded chroma 4x4 TBs of one class are packed in decode order at upload (upload_host.cpp pack_picture), so the
 // coded TBs of a region normally sit in consecutive 16-sample slots.  Straight-line, as quad_jobs.
 __device__ __forceinline__ bool cquad_jobs(const ChromaJobLds* j, uint32_t zero_off, uint32_t& base, uint32_t& codes) {
     const uint32_t o = j[0].w0 & 0x1fffu;
@@ -198,7 +198,7 @@ __device__ __forceinline__ void prep_job_store(IntraJob* dst, const IntraJob& J)
 
 // grid (CTUs, pictures), 64 threads: one wave per CTU walks its TBs 64 at a time.  A CTU's
 // job list is [chroma jobs][luma jobs]; both are staged in LDS (luma words 0, 1, 2, 3, 5, at
-// most 256 jobs per CTU; chroma words 0..5, at most 128; p265r.hip validate_picture) so that
+// most 256 jobs per CTU; chroma words 0..5, at most 128; upload_host.cpp validate_picture) so that
 // luma and chroma 4x4 quads can be merged before the lists are written, compacted.
 constexpr int kMaxCtuLuma = 256;
 constexpr int kMaxCtuChroma = 128;

@@ -264,7 +264,7 @@ struct RowCtrl {                 // 256 B at the start of dynamic LDS
 // half empty for the younger one's tail.  Each workgroup takes a rank in its CU's slot (one
 // atomic add at start; slot = XCC id x 128 + CU / SH / SE id), publishes the rows it has
 // dequeued, and at every row start runs at priority 1 while it is behind its partner.
-constexpr int kRowCuSlots = 2048;
+// (kRowCuSlots of them per batch: batch_types.h)
 struct RowCuSlot { int count; int prog[3]; };
 // Dynamic LDS layout: [RowCtrl 256 B][prog: fs x hc ints][W x WaveLds][fs x 2 line buffers][AngTab4][AngTab8]
 // prog[slot][cy] = (local picture index & 0xffff) << 16 | CTUs done.

@@ -10,7 +10,6 @@
 
 #include <algorithm>
 #include <array>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +17,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/p265r.h"
@@ -34,8 +32,8 @@
 #include "sao.h"
 #include "sao_strip16.h"
 #include "sao_rows.h"
-#include "sparse_host.h"
 #include "tables.h"
+#include "upload_host.h"
 
 using namespace p265r;
 
@@ -59,10 +57,6 @@ using namespace p265r;
 #ifndef P265R_SAO_AUX
 #define P265R_SAO_AUX 0            // pipelined chip-filling batches: prep on the lane stream, the loop filters on the
                                    // lane's aux stream, so the next run's residual + prep overlap this run's SAO
-#endif
-#ifndef P265R_UP_STREAM
-#define P265R_UP_STREAM 0          // 0: a batch uploads on its own lane stream; 1: on an upload stream created with
-                                   // the context; 2: created at the first upload (after the lanes)
 #endif
 #ifndef P265R_EXPAND_STREAM
 #define P265R_EXPAND_STREAM 0      // sparse upload: 0 the expand kernels follow their chunk's copies on the upload's
@@ -88,22 +82,7 @@ int hip_fail(hipError_t e, const char* what) {
         if (_e != hipSuccess) return hip_fail(_e, #expr);    \
     } while (0)
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-enum { RC_RAW = RC_NUM, N_POOLS = RC_NUM + 1 };
-
 constexpr size_t kDlHalf = 24u << 20;   // download bounce buffer half (p265r_batch_download)
-
-int tb_class(const p265r_tb& t) {
-    if (t.flags & (P265R_TB_BYPASS | P265R_TB_PCM)) return RC_RAW;
-    if (t.flags & P265R_TB_TSKIP) return RC_TSKIP;
-    switch (t.log2_size) {
-        case 2: return t.c_idx == 0 ? RC_DST4 : RC_DCT4;
-        case 3: return RC_DCT8;
-        case 4: return RC_DCT16;
-        default: return RC_DCT32;
-    }
-}
 
 bool params_ok(const p265r_params& p) {
     return p.version == P265R_ABI_VERSION && p.chroma_format_idc == 1 && p.pic_width > 0 && p.pic_height > 0 &&
@@ -116,8 +95,6 @@ bool params_ok(const p265r_params& p) {
 struct p265r_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t up_stream = nullptr;   // uploads: never queued behind a lane's kernels, so batch k+1
-                                       // uploads while batch k decodes (the host waits for it alone)
     p265r_params params{};
     Geo geo{};
     int n_ctus = 0;
@@ -236,25 +213,6 @@ struct p265r_batch {
 
 namespace {
 
-// Run fn(i) for i in [0, n) on up to 16 host threads (picture-level packing work).
-template <class F>
-void parallel_for(int n, F fn) {
-    const int hw = (int)std::max(1u, std::thread::hardware_concurrency());
-    const int nt = std::min(std::min(hw, 16), n);
-    if (nt <= 1) {
-        for (int i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<int> next{0};
-    std::vector<std::thread> th;
-    th.reserve(nt);
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) fn(i);
-        });
-    for (auto& t : th) t.join();
-}
-
 // a lane stream: default priority, or the device's highest with P265R_STREAM_PRIO (then the
 // dispatcher prefers the lanes' residual / intra / SAO workgroups over the prep streams')
 hipError_t lane_stream_create(const p265r_ctx* ctx, hipStream_t* st) {
@@ -263,75 +221,6 @@ hipError_t lane_stream_create(const p265r_ctx* ctx, hipStream_t* st) {
     hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
     if (e != hipSuccess) return e;
     return hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest);
-}
-
-// a picture's luma size: its own (p265r_picture.pic_width / pic_height) or the context's
-std::array<int, 2> pic_size(const p265r_ctx* ctx, const p265r_picture& pic) {
-    return {pic.pic_width ? (int)pic.pic_width : (int)ctx->params.pic_width,
-            pic.pic_height ? (int)pic.pic_height : (int)ctx->params.pic_height};
-}
-
-// p265r_tb.qp (qP incl. QpBdOffset of the TB's component) is 0 .. 51 + 6 * (BitDepth - 8) (8.6.1).  PCM TBs
-// too: a luma TB's qp goes into the deblocking map entry beside the edge bits (dbk_map_kernel: one byte at 8
-// bits, where 64 and above would set them), and a coded TB's qp / 6 sets Dequant's shift (residual.h).
-inline bool qp_ok(const p265r_params& p, const p265r_tb& t) {
-    return t.qp <= 51 + 6 * ((t.c_idx ? p.bit_depth_chroma : p.bit_depth_luma) - 8);
-}
-
-// (sparse: the picture of a sparse upload -- its transformed TBs' coef_off index entries, checked by
-// sparse_validate_tb in the upload's counting pass)
-int validate_picture(const p265r_ctx* ctx, const p265r_picture& pic, bool sparse = false) {
-    const p265r_params& p = ctx->params;
-    const auto sz = pic_size(ctx, pic);
-    const int pw = sz[0], ph = sz[1];
-    if (pw > p.pic_width || ph > p.pic_height || pw % 8 || ph % 8 || pw <= 0 || ph <= 0) return P265R_EINVAL;
-    if (pic.reserved) return P265R_EINVAL;
-    Geo g = ctx->geo;
-    g.wc = (pw + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
-    g.hc = (ph + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
-    const int n_ctus = g.wc * g.hc;
-    if (!pic.ctus || (!pic.tbs && pic.n_tbs) || (!pic.coef && pic.n_coef)) return P265R_EINVAL;
-    if (pic.flags & ~P265R_PIC_RECON_INPUT) return P265R_EINVAL;
-    if ((pic.flags & P265R_PIC_RECON_INPUT) && (!pic.recon[0] || !pic.recon[1] || !pic.recon[2])) return P265R_EINVAL;
-    const int ctb = 1 << p.ctb_log2_size;
-    const int max_tbs = 3 * (ctb / 4) * (ctb / 4) / 2;                  // all-4x4 luma + 4x4 chroma per 8x8
-    for (int rs = 0; rs < n_ctus; ++rs) {
-        const p265r_ctu& c = pic.ctus[rs];
-        if ((uint64_t)c.tb_begin + c.tb_count > pic.n_tbs) return P265R_ERANGE;
-        if (c.tb_count > max_tbs) return P265R_EINVAL;                  // more TBs than 4x4 units
-        for (int k = 0; k < 2; ++k) {
-            const int v = ((c.deblock_offsets >> (4 * k)) & 15) ^ 8;   // biased: -6..6 -> 2..14
-            if (v < 2 || v > 14) return P265R_EINVAL;
-        }
-        for (int k = 0; k < 3; ++k) {
-            if (c.sao_type[k] > 2) return P265R_EINVAL;
-            if (c.sao_type[k] == 2 && c.sao_class[k] > 3) return P265R_EINVAL;
-            if (c.sao_type[k] == 1 && c.sao_class[k] > 31) return P265R_EINVAL;
-        }
-        // Cb and Cr share SaoTypeIdx and SaoEoClass (7.4.9.3.2; sao.py:57-59, 75-77)
-        if (c.sao_type[1] != c.sao_type[2] || (c.sao_type[1] == 2 && c.sao_class[1] != c.sao_class[2])) return P265R_EINVAL;
-        const int cx0 = (rs % g.wc) * ctb, cy0 = (rs / g.wc) * ctb;
-        int n_luma = 0, n_chroma = 0;
-        for (uint32_t i = c.tb_begin; i < c.tb_begin + c.tb_count; ++i) {
-            const p265r_tb& t = pic.tbs[i];
-            if (t.c_idx == 0 && ++n_luma > (ctb / 4) * (ctb / 4)) return P265R_EINVAL;   // intra_prep.h kMaxCtuLuma
-            if (t.c_idx && ++n_chroma > 2 * (ctb / 8) * (ctb / 8)) return P265R_EINVAL;  // kMaxCtuChroma
-            if (t.log2_size < 2 || t.log2_size > 5 || t.c_idx > 2 || t.pred_mode > 34) return P265R_EINVAL;
-            if (t.c_idx && t.log2_size > 4) return P265R_EINVAL;        // 4:2:0 chroma TBs are 4..16
-            if (!qp_ok(p, t)) return P265R_EINVAL;
-            const int sub = t.c_idx ? 1 : 0;
-            const int n = 1 << t.log2_size;
-            const int xl = t.x << sub, yl = t.y << sub, nl = n << sub;
-            if (xl + nl > pw || yl + nl > ph) return P265R_ERANGE;
-            if (xl < cx0 || yl < cy0 || xl + nl > cx0 + ctb || yl + nl > cy0 + ctb) return P265R_ERANGE;
-            if ((t.x & 3) || (t.y & 3) || (t.x & (n - 1)) || (t.y & (n - 1))) return P265R_EINVAL;
-            if ((t.flags & (P265R_TB_CBF | P265R_TB_PCM)) && !(sparse && tb_is_sparse(t))) {
-                if ((uint64_t)t.coef_off + (uint64_t)n * n > pic.n_coef) return P265R_ERANGE;
-            }
-            if (t.flags & ~0x0fu) return P265R_EINVAL;
-        }
-    }
-    return P265R_OK;
 }
 
 #ifdef P265R_DEBUG_DIAG
@@ -682,7 +571,6 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     if (e == hipSuccess) e = hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e == hipSuccess) e = lane_stream_create(ctx, &ctx->stream);
     if (e == hipSuccess) ctx->lanes.push_back(ctx->stream);
-    if (e == hipSuccess && P265R_UP_STREAM == 1) e = hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking);
     if (e == hipSuccess) {
         int8_t ang[35];
         int16_t inv[35];
@@ -722,7 +610,6 @@ void p265r_destroy(p265r_ctx* ctx) {
     for (auto& r : ctx->runs) for (auto& e : r.ev) (void)hipEventDestroy(e);
     for (auto& e : ctx->spare) (void)hipEventDestroy(e);
     for (size_t i = 1; i < ctx->lanes.size(); ++i) (void)hipStreamDestroy(ctx->lanes[i]);
-    if (ctx->up_stream) (void)hipStreamDestroy(ctx->up_stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->cache_mem) (void)hipFree(ctx->cache_mem);
     if (ctx->d_sf) (void)hipFree(ctx->d_sf);
@@ -739,375 +626,178 @@ void p265r_destroy(p265r_ctx* ctx) {
 
 namespace {
 
+// The context's staging buffer (grow-only, reused across uploads) with room for `need` bytes: pinned, or
+// pageable when pinning fails.
+int stage_reserve(p265r_ctx* ctx, size_t need) {
+    if (ctx->stage_bytes >= need) return P265R_OK;
+    if (ctx->stage) { if (ctx->stage_pinned) (void)hipHostFree(ctx->stage); else std::free(ctx->stage); }
+    ctx->stage = nullptr;
+    ctx->stage_bytes = 0;
+    const size_t want = need + need / 4;
+    void* ptr = nullptr;
+    if (hipHostMalloc(&ptr, want, hipHostMallocDefault) == hipSuccess) {
+        ctx->stage_pinned = true;
+    } else {
+        (void)hipGetLastError();
+        ptr = std::malloc(want);
+        ctx->stage_pinned = false;
+        if (!ptr) return P265R_ENOMEM;
+    }
+    ctx->stage = static_cast<unsigned char*>(ptr);
+    ctx->stage_bytes = want;
+    return P265R_OK;
+}
+
+// The batch's device allocation of `total` bytes: the context's cached one (the last freed) when it is large
+// enough, else a new one -- dropping the cached one if that makes the room.
+int batch_mem_take(p265r_ctx* ctx, p265r_batch* b, size_t total) {
+    if (ctx->cache_mem && ctx->cache_bytes >= total) {
+        b->mem = ctx->cache_mem;
+        b->bytes = ctx->cache_bytes;
+        ctx->cache_mem = nullptr;
+        ctx->cache_bytes = 0;
+        return P265R_OK;
+    }
+    hipError_t e = hipMalloc(&b->mem, total);
+    if (e != hipSuccess && ctx->cache_mem) {
+        (void)hipGetLastError();
+        (void)hipFree(ctx->cache_mem);
+        ctx->cache_mem = nullptr;
+        ctx->cache_bytes = 0;
+        e = hipMalloc(&b->mem, total);
+    }
+    if (e != hipSuccess) return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc");
+    b->bytes = total;
+    return P265R_OK;
+}
+
+// The context's device landing buffer of a sparse upload's entries + begin words (grow-only).
+int landing_reserve(p265r_ctx* ctx, size_t need) {
+    if (ctx->sp_bytes >= need) return P265R_OK;
+    if (ctx->sp_mem) (void)hipFree(ctx->sp_mem);
+    ctx->sp_mem = nullptr;
+    ctx->sp_bytes = 0;
+    const size_t want = need + need / 4;
+    const hipError_t e = hipMalloc(&ctx->sp_mem, want);
+    if (e != hipSuccess) {
+        ctx->sp_mem = nullptr;
+        return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc");
+    }
+    ctx->sp_bytes = want;
+    return P265R_OK;
+}
+
+// Sparse upload: expand the entries of nj jobs of class c (jobs, their begin words beg; their TBs are pool
+// elements [q0, q1)) into the coefficient pool, on stream xs.
+hipError_t launch_expand(hipStream_t xs, int16_t* d_pool, int c, const ResJob* jobs, int nj, size_t q0, size_t q1,
+                         const uint32_t* beg, const uint32_t* d_ent) {
+#if P265R_EXPAND_SCATTER
+    const hipError_t e = hipMemsetAsync(d_pool + q0, 0, sizeof(int16_t) * (q1 - q0), xs);
+    if (e != hipSuccess) return e;
+    switch (c) {
+        case RC_DST4: case RC_DCT4: case RC_TSKIP: coef_scatter_kernel<1><<<(nj + 255) / 256, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
+        case RC_DCT8: coef_scatter_kernel<4><<<(nj + 63) / 64, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
+        case RC_DCT16: coef_scatter_kernel<16><<<(nj + 15) / 16, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
+        default: coef_scatter_kernel<64><<<(nj + 3) / 4, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
+    }
+#else
+    (void)q1;
+    const int per_block = kExpandWaves * kExpandTile;    // int16 per block of a fixed-size class
+    switch (c) {
+        case RC_DST4: case RC_DCT4:
+            coef_expand_kernel<2><<<(unsigned)(((size_t)nj * 16 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(d_pool, q0, beg, d_ent, nj); break;
+        case RC_DCT8:
+            coef_expand_kernel<3><<<(unsigned)(((size_t)nj * 64 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(d_pool, q0, beg, d_ent, nj); break;
+        case RC_DCT16:
+            coef_expand_kernel<4><<<(unsigned)(((size_t)nj * 256 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(d_pool, q0, beg, d_ent, nj); break;
+        case RC_DCT32:
+            coef_expand_kernel<5><<<(unsigned)(((size_t)nj * 1024 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(d_pool, q0, beg, d_ent, nj); break;
+        default:
+            coef_expand_jobs_kernel<<<(unsigned)((nj + kExpandWaves - 1) / kExpandWaves), 64 * kExpandWaves, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
+    }
+#endif
+    return hipGetLastError();
+}
+
 // The upload of p265r_batch_upload (sp null: dense coefficients) and p265r_batch_upload_sparse (sp[i]: the
-// entries of pics[i]'s transformed TBs).  Layout, chunking, staging and the device image are the same; the
-// sparse one stages, per chunk, the entries of each class slab in job order and one entry-begin word per job
-// instead of the slabs, and expands them on the device after the chunk's copies (coef_expand.h).
+// entries of pics[i]'s transformed TBs): plan (upload_host.h: validation, layout, chunking), allocate, then per
+// chunk pack, copy and -- sparse -- expand on the device (coef_expand.h), then the header and the join.
 int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_coef* sp, int n_pics, p265r_batch** out) {
     if (!ctx || !pics || n_pics <= 0 || !out) return P265R_EINVAL;
 #if P265R_EXPERIMENTS
     // P265R_UPLOAD_TIMES=1 (experiments build): wall time of the upload's stages on stderr
     const bool ut = std::getenv("P265R_UPLOAD_TIMES") != nullptr;
     std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> tp;
-#define P265R_UT(name) do { if (ut) tp.emplace_back(name, std::chrono::steady_clock::now()); } while (0)
+#define P265R_UT_AT(name, t) do { if (ut) tp.emplace_back(name, t); } while (0)
 #else
-#define P265R_UT(name) do { } while (0)
+#define P265R_UT_AT(name, t) do { } while (0)
 #endif
+#define P265R_UT(name) P265R_UT_AT(name, std::chrono::steady_clock::now())
     P265R_UT("start");
     *out = nullptr;
-    if (n_pics > 65535) return P265R_ERANGE;                     // pictures index a grid dimension
-    for (int i = 0; i < n_pics; ++i)
-        if ((pics[i].flags ^ pics[0].flags) & P265R_PIC_RECON_INPUT) return P265R_EINVAL;
-    const bool recon_input = (pics[0].flags & P265R_PIC_RECON_INPUT) != 0;
-    const Geo& g = ctx->geo;
-    const int nc = ctx->n_ctus;                  // per-picture slots of the context size
-    // per picture: luma size, CTUs, no-filter map bytes (a ragged batch mixes sizes)
-    std::vector<std::array<int, 2>> psize(n_pics);
-    std::vector<int> pnc(n_pics);
-    std::vector<size_t> pnf(n_pics);
-    bool ragged = false;
-    for (int i = 0; i < n_pics; ++i) {
-        psize[i] = pic_size(ctx, pics[i]);
-        const int wc = (psize[i][0] + (1 << g.ctb_log2) - 1) >> g.ctb_log2, hc = (psize[i][1] + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
-        pnc[i] = wc * hc;
-        pnf[i] = (size_t)((psize[i][0] + 7) / 8) * ((psize[i][1] + 7) / 8);
-        ragged |= psize[i][0] != g.w || psize[i][1] != g.h;
-    }
-    // ---- pool sizing per class (per picture, so pictures can be packed in parallel) ----
-    std::vector<std::array<size_t, N_POOLS>> cnt_pool(n_pics);
-    std::vector<std::array<int, RC_NUM>> cnt_job(n_pics);
-    std::vector<int> crc(n_pics, 0);
-    std::vector<std::array<size_t, RC_NUM>> cnt_nz(sp ? n_pics : 0);    // sparse: entries per class
-    parallel_for(n_pics, [&](int i) {
-        // every record of every picture is checked (on up to 16 host threads: pictures are independent; the
-        // first failing picture's code is returned), then its coded TBs are counted per class with
-        // thread-local counters, stored once (neighbouring pictures' counters share cache lines).  Every TB
-        // of the array is packed, so the fields the packing reads are checked here for all of them
-        // (validate_picture checks the TBs the CTUs reference, by position); one pass per picture right
-        // after its validation, while its TB array is still in the cache
-        const p265r_picture& pic = pics[i];
-        if ((crc[i] = validate_picture(ctx, pic, sp != nullptr)) != 0) return;
-        // (sparse: every entry of every TB is checked here, on the host, in the same pass -- the expand
-        // kernel trusts pos)
-        if (sp && !sp[i].nz && sp[i].n_nz) { crc[i] = P265R_EINVAL; return; }
-        std::array<size_t, N_POOLS> cp{};
-        std::array<int, RC_NUM> cj{};
-        std::array<size_t, RC_NUM> cn{};
-        for (uint32_t t = 0; t < pic.n_tbs; ++t) {
-            const p265r_tb& tb = pic.tbs[t];
-            if (sp) {                                  // (a local code: crc's elements share cache lines)
-                const int rc = sparse_validate_tb(tb, sp[i].nz, sp[i].n_nz, pic.n_coef);
-                if (rc) { crc[i] = rc; return; }
-            }
-            if (!(tb.flags & (P265R_TB_CBF | P265R_TB_PCM))) continue;
-            if (tb.log2_size < 2 || tb.log2_size > 5 || tb.c_idx > 2 || !qp_ok(ctx->params, tb)) { crc[i] = P265R_EINVAL; return; }
-            const bool sparse_tb = sp && tb_is_sparse(tb);
-            if (!sparse_tb && (uint64_t)tb.coef_off + ((uint64_t)1 << (2 * tb.log2_size)) > pic.n_coef) { crc[i] = P265R_ERANGE; return; }
-            const int cls = tb_class(tb);
-            cp[cls] += (size_t)1 << (2 * tb.log2_size);
-            if (cls < RC_NUM) ++cj[cls];
-            if (sparse_tb) cn[cls] += tb_sparse_count(tb);
-        }
-        cnt_pool[i] = cp;
-        cnt_job[i] = cj;
-        if (sp) cnt_nz[i] = cn;
-    });
-    for (int i = 0; i < n_pics; ++i)
-        if (crc[i]) return crc[i];
-    P265R_UT("validate+count");
-    size_t pool_sz[N_POOLS] = {};
-    size_t n_tbs_total = 0;
-    int n_jobs[RC_NUM] = {};
-    for (int i = 0; i < n_pics; ++i) {
-        n_tbs_total += pics[i].n_tbs;
-        for (int c = 0; c < N_POOLS; ++c) pool_sz[c] += cnt_pool[i][c];
-        for (int c = 0; c < RC_NUM; ++c) n_jobs[c] += cnt_job[i][c];
-    }
-    size_t pool_base[N_POOLS];
-    size_t pool_total = 0;
-    for (int c = 0; c < N_POOLS; ++c) { pool_base[c] = pool_total; pool_total += pool_sz[c]; }
-    // the row kernel addresses every residual as a signed 32-bit int16 offset relative to the
-    // residual pool: raw samples down to -(pool_total + 128) (coefficient pool + its pad), the
-    // zero block and the fast jobs' over-read up to pool_total + 512 + 64
-    if (pool_total + 2048 > (size_t)INT32_MAX) return P265R_ERANGE;
-    // ---- device layout -----------------------------------------------------------
-    const bool sao = ctx->params.sample_adaptive_offset != 0;
-    bool dbk = false;
-    for (int i = 0; i < n_pics && !dbk; ++i)
-        for (int rs = 0; rs < pnc[i]; ++rs)
-            if (pics[i].ctus[rs].flags & P265R_CTU_DEBLOCK) { dbk = true; break; }
-    const bool lf = sao || dbk;                  // separate output planes
-    const size_t pb = g.pel16 ? 2 : 1;          // bytes per sample
-    const size_t plane_bytes[3] = {(size_t)g.stride[0] * g.h * pb, (size_t)g.stride[1] * g.ch * pb, (size_t)g.stride[2] * g.ch * pb};
-    const size_t pic_plane_bytes = align_up(plane_bytes[0], 256) + 2 * align_up(plane_bytes[1], 256);
-    size_t off = 0;
-    const size_t o_pics = off; off = align_up(off + sizeof(DevPic) * n_pics, 256);
-    // error word (+ the row kernel's per-CU workgroup slots, kRowCuSlots x 16 B, intra_rows.h)
-    // cross-group row kernel (a batch whose chains fit xg workgroups each on the CUs): its progress words
-    // follow the CU slots (cleared together per run), its lines get their own range
-    const bool xg_ok = ctx->xg > 0 && ctx->split && 2 * (long long)n_pics * ctx->xg <= ctx->num_cus;
-    // (+ one row ticket per chain)
-    const size_t xg_prog_bytes = xg_ok ? sizeof(int) * 2 * ((size_t)g.hc + 1) * n_pics : 0;
-    const size_t o_err = off; off = align_up(off + 256 + kRowCuSlots * 16 + xg_prog_bytes, 256);
-    const size_t o_xgl = off;
-    if (xg_ok) off = align_up(off + 2 * (size_t)g.hc * ((size_t)(g.wc + 2) << g.ctb_log2) * n_pics, 256);
-    const size_t o_ctus = off; off = align_up(off + sizeof(p265r_ctu) * nc * (size_t)n_pics, 256);
-    const size_t o_tbs = off; off = align_up(off + sizeof(p265r_tb) * n_tbs_total, 256);
-    // both pools padded by 64 B: the intra kernel reads fixed-shape 32-B runs
-    // (the row kernel reads every residual relative to the residual pool: raw TBs at negative
-    // offsets into the coefficient pool, uncoded halves from a zero block after the residuals;
-    // fast jobs read one sample per lane, lanes past the TB up to 126 B beyond it)
-    const size_t o_pool = off; off = align_up(off + sizeof(int16_t) * pool_total + 256, 256);
-    const size_t o_res = off; off = align_up(off + sizeof(int16_t) * pool_total + 1024, 256);
-    size_t o_jobs[RC_NUM];
-    for (int c = 0; c < RC_NUM; ++c) { o_jobs[c] = off; off = align_up(off + sizeof(ResJob) * n_jobs[c], 256); }
-    // intra jobs (same index space as the TB records) + per-CTU job counts
-    const size_t o_ijobs = off; off = align_up(off + sizeof(IntraJob) * n_tbs_total, 256);
-    const size_t o_jcount = off; off = align_up(off + 4 * sizeof(uint32_t) * nc * (size_t)n_pics, 256);
-    size_t o_nf = off;
-    size_t nf_bytes = (size_t)g.nf_w * ((g.h + 7) / 8);
-    size_t n_nf = 0;
-    for (int i = 0; i < n_pics; ++i) n_nf += pics[i].nofilter ? 1 : 0;
-    off = align_up(off + nf_bytes * n_nf, 256);
-    const size_t map_bytes = nf_bytes << g.pel16;                  // uint16 entries above 8 bits (loopfilter.h)
-    const size_t o_map = off; if (dbk) off = align_up(off + map_bytes * n_pics, 256);
-    const size_t o_rec = off; off += pic_plane_bytes * n_pics;
-    const size_t o_out = off; if (lf) off += pic_plane_bytes * n_pics;
-    const size_t total = align_up(off, 256);
+    UploadPlan plan;
+    std::chrono::steady_clock::time_point counted;
+    if (const int rc = plan_upload(ctx->params, ctx->geo, ctx->n_ctus, ctx->xg, ctx->split != 0, ctx->num_cus, pics, sp, n_pics, &plan,
+                                   P265R_EXPERIMENTS ? &counted : nullptr))
+        return rc;
+    P265R_UT_AT("validate+count", counted);
     P265R_UT("layout");
-
-    // ---- host staging: [0, o_res) | jobs [o_jobs[0], o_ijobs) | no-filter maps, compact ---------
-    // (sparse: of the pool only the raw slab is staged, at o_pool; behind the no-filter maps follow, per
-    // chunk, the entries [class][job order] and the begin words [class][job + 1 closing word])
-    const size_t jobs_bytes = o_ijobs - o_jobs[0];
-    const size_t s_jobs = sp ? align_up(o_pool + sizeof(int16_t) * pool_sz[RC_RAW], 256) : o_res, s_nf = s_jobs + jobs_bytes;
-    // (16 chunks of 32 pictures at 512: the first H2D starts after 1/16 of the packing; 4 chunks measured
-    // 78 ms per 512 1080p pictures, H2D-bound from the first chunk on)
-    const int n_chunks = std::max(1, std::min(n_pics / 8, 16));
-    size_t nz_total = 0, n_jobs_total = 0;
-    for (int i = 0; sp && i < n_pics; ++i)
-        for (int c = 0; c < RC_NUM; ++c) nz_total += cnt_nz[i][c];
-    for (int c = 0; c < RC_NUM; ++c) n_jobs_total += (size_t)n_jobs[c];
-    if (nz_total > (size_t)UINT32_MAX) return P265R_ERANGE;         // begin words are 32-bit entry indices
-    const size_t beg_words = sp ? n_jobs_total + (size_t)n_chunks * RC_NUM : 0;
-    const size_t s_ent = align_up(s_nf + nf_bytes * n_nf, 256), s_beg = s_ent + align_up(sizeof(uint32_t) * nz_total, 256);
-    const size_t sp_need = sp ? align_up(sizeof(uint32_t) * nz_total, 256) + align_up(sizeof(uint32_t) * beg_words, 256) : 0;
-    const size_t stage_need = sp ? s_ent + sp_need : s_nf + nf_bytes * n_nf;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stage_bytes < stage_need) {
-        if (ctx->stage) { if (ctx->stage_pinned) (void)hipHostFree(ctx->stage); else std::free(ctx->stage); }
-        ctx->stage = nullptr;
-        ctx->stage_bytes = 0;
-        const size_t want = stage_need + stage_need / 4;
-        void* ptr = nullptr;
-        if (hipHostMalloc(&ptr, want, hipHostMallocDefault) == hipSuccess) {
-            ctx->stage_pinned = true;
-        } else {
-            (void)hipGetLastError();
-            ptr = std::malloc(want);
-            ctx->stage_pinned = false;
-            if (!ptr) return P265R_ENOMEM;
-        }
-        ctx->stage = static_cast<unsigned char*>(ptr);
-        ctx->stage_bytes = want;
-    }
+    if (const int rc = stage_reserve(ctx, plan.stage_need)) return rc;
     unsigned char* host = ctx->stage;
     p265r_batch* b = new (std::nothrow) p265r_batch();
     if (!b) return P265R_ENOMEM;
-    hipError_t e = hipSuccess;
-    if (ctx->cache_mem && ctx->cache_bytes >= total) {      // reuse the last freed allocation
-        b->mem = ctx->cache_mem;
-        b->bytes = ctx->cache_bytes;
-        ctx->cache_mem = nullptr;
-        ctx->cache_bytes = 0;
-    } else {
-        e = hipMalloc(&b->mem, total);
-        if (e != hipSuccess && ctx->cache_mem) {             // make room: drop the cached one
-            (void)hipGetLastError();
-            (void)hipFree(ctx->cache_mem);
-            ctx->cache_mem = nullptr;
-            ctx->cache_bytes = 0;
-            e = hipMalloc(&b->mem, total);
-        }
-        if (e != hipSuccess) { delete b; return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc"); }
-        b->bytes = total;
-    }
-    if (sp && ctx->sp_bytes < sp_need) {                     // landing buffer of the entries + begin words
-        if (ctx->sp_mem) (void)hipFree(ctx->sp_mem);
-        ctx->sp_mem = nullptr;
-        ctx->sp_bytes = 0;
-        const size_t want = sp_need + sp_need / 4;
-        e = hipMalloc(&ctx->sp_mem, want);
-        if (e != hipSuccess) {
-            ctx->sp_mem = nullptr;
-            (void)hipFree(b->mem);
-            delete b;
-            return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc");
-        }
-        ctx->sp_bytes = want;
-    }
+    if (const int rc = batch_mem_take(ctx, b, plan.total)) { delete b; return rc; }
+    if (const int rc = landing_reserve(ctx, plan.sp_need)) { (void)hipFree(b->mem); delete b; return rc; }
     b->n_pics = n_pics;
     b->stream = ctx->stream;
     if (ctx->pipeline > 1) {
         b->lane = ctx->next_lane++ % ctx->pipeline;
         b->stream = ctx->lanes[b->lane];
     }
-    b->sao = sao;
-    b->dbk = dbk;
-    b->recon_input = recon_input;
-    b->ragged = ragged;
-    b->size = psize;
+    b->sao = plan.sao;
+    b->dbk = plan.dbk;
+    b->recon_input = plan.recon_input;
+    b->ragged = plan.ragged;
+    b->size = plan.psize;
     unsigned char* dbase = static_cast<unsigned char*>(b->mem);
-    b->d_pics = reinterpret_cast<DevPic*>(dbase + o_pics);
-    b->d_pool = reinterpret_cast<int16_t*>(dbase + o_pool);
-    b->d_res = reinterpret_cast<int16_t*>(dbase + o_res);
-    b->d_err = reinterpret_cast<int*>(dbase + o_err);
-    b->d_xg_prog = xg_ok ? b->d_err + 64 + kRowCuSlots * 4 : nullptr;
-    b->d_xg_lines = xg_ok ? dbase + o_xgl : nullptr;
+    b->d_pics = reinterpret_cast<DevPic*>(dbase + plan.o_pics);
+    b->d_pool = reinterpret_cast<int16_t*>(dbase + plan.o_pool);
+    b->d_res = reinterpret_cast<int16_t*>(dbase + plan.o_res);
+    b->d_err = reinterpret_cast<int*>(dbase + plan.o_err);
+    b->d_xg_prog = plan.xg_ok ? b->d_err + 64 + kRowCuSlots * 4 : nullptr;
+    b->d_xg_lines = plan.xg_ok ? dbase + plan.o_xgl : nullptr;
     for (int c = 0; c < RC_NUM; ++c) {
-        b->d_jobs[c] = reinterpret_cast<ResJob*>(dbase + o_jobs[c]);
-        b->n_jobs[c] = n_jobs[c];
-        b->slab[c] = (uint32_t)pool_base[c];
+        b->d_jobs[c] = reinterpret_cast<ResJob*>(dbase + plan.o_jobs[c]);
+        b->n_jobs[c] = plan.n_jobs[c];
+        b->slab[c] = (uint32_t)plan.pool_base[c];
     }
+    b->view.rec0 = dbase + plan.o_rec;
+    b->view.out0 = plan.lf ? dbase + plan.o_out : dbase + plan.o_rec;
+    b->view.pic_bytes = plan.pic_plane_bytes;
+    for (int c = 0; c < 3; ++c) b->view.plane_off[c] = plan.plane_off[c];
+    b->view.ctus0 = reinterpret_cast<const p265r_ctu*>(dbase + plan.o_ctus);
+    b->view.err = b->d_err;
     b->h_pics.resize(n_pics);
-
     P265R_UT("alloc");
-    p265r_ctu* h_ctus = reinterpret_cast<p265r_ctu*>(host + o_ctus);
-    p265r_tb* h_tbs = reinterpret_cast<p265r_tb*>(host + o_tbs);
-    int16_t* h_pool = reinterpret_cast<int16_t*>(host + o_pool);
-    ResJob* h_jobs[RC_NUM];
-    for (int c = 0; c < RC_NUM; ++c) h_jobs[c] = reinterpret_cast<ResJob*>(host + s_jobs + (o_jobs[c] - o_jobs[0]));
-    // per-picture start offsets in every pool / job list / TB array / no-filter slot
-    std::vector<std::array<size_t, N_POOLS>> pool_at(n_pics);
-    std::vector<std::array<int, RC_NUM>> job_at(n_pics);
-    std::vector<size_t> tb_at(n_pics), nf_at(n_pics);
-    {
-        size_t pf[N_POOLS];
-        std::copy(pool_base, pool_base + N_POOLS, pf);
-        int jf[RC_NUM] = {};
-        size_t tf = 0, nf = 0;
-        for (int i = 0; i < n_pics; ++i) {
-            for (int c = 0; c < N_POOLS; ++c) { pool_at[i][c] = pf[c]; pf[c] += cnt_pool[i][c]; }
-            for (int c = 0; c < RC_NUM; ++c) { job_at[i][c] = jf[c]; jf[c] += cnt_job[i][c]; }
-            tb_at[i] = tf;
-            tf += pics[i].n_tbs;
-            nf_at[i] = nf;
-            nf += pics[i].nofilter ? 1 : 0;
-        }
-    }
-    auto chunk_lo = [&](int k) { return (int)((long long)n_pics * k / n_chunks); };
-    // sparse: where each picture's entries and begin words of every class go (chunk-major, then class, then
-    // picture), and where each chunk's class ranges start (ent_kc / beg_kc [k * RC_NUM + c]; [n_chunks * RC_NUM]
-    // closes the last)
-    std::vector<std::array<size_t, RC_NUM>> ent_at(sp ? n_pics : 0), beg_at(sp ? n_pics : 0);
-    std::vector<size_t> ent_kc, beg_kc;
-    if (sp) {
-        size_t ef = 0, bf = 0;
-        for (int k = 0; k < n_chunks; ++k)
-            for (int c = 0; c < RC_NUM; ++c) {
-                ent_kc.push_back(ef);
-                beg_kc.push_back(bf);
-                for (int i = chunk_lo(k); i < chunk_lo(k + 1); ++i) {
-                    ent_at[i][c] = ef; ef += cnt_nz[i][c];
-                    beg_at[i][c] = bf; bf += (size_t)cnt_job[i][c];
-                }
-                ++bf;                                            // the class range's closing word
-            }
-        ent_kc.push_back(ef);
-        beg_kc.push_back(bf);
-    }
-    uint32_t* h_ent = sp ? reinterpret_cast<uint32_t*>(host + s_ent) : nullptr;
-    uint32_t* h_beg = sp ? reinterpret_cast<uint32_t*>(host + s_beg) : nullptr;
-    int16_t* h_raw = reinterpret_cast<int16_t*>(host + o_pool);     // sparse: the raw slab alone
-    auto pack_pic = [&](int i) {
-        const p265r_picture& pic = pics[i];
-        std::memcpy(h_ctus + (size_t)i * nc, pic.ctus, sizeof(p265r_ctu) * pnc[i]);
-        if (pnc[i] < nc) std::memset(h_ctus + (size_t)i * nc + pnc[i], 0, sizeof(p265r_ctu) * (nc - pnc[i]));
-        p265r_tb* tb_dst = h_tbs + tb_at[i];
-        size_t pool_fill[N_POOLS];
-        int job_fill[RC_NUM];
-        for (int c = 0; c < N_POOLS; ++c) pool_fill[c] = pool_at[i][c];
-        for (int c = 0; c < RC_NUM; ++c) job_fill[c] = job_at[i][c];
-        size_t ent_fill[RC_NUM] = {}, beg_fill[RC_NUM] = {};
-        for (int c = 0; sp && c < RC_NUM; ++c) { ent_fill[c] = ent_at[i][c]; beg_fill[c] = beg_at[i][c]; }
-        for (uint32_t t = 0; t < pic.n_tbs; ++t) {
-            p265r_tb tb = pic.tbs[t];
-            if (sp) std::memset(tb.reserved, 0, sizeof(tb.reserved));     // (the entry count: not part of the image)
-            if (tb.flags & (P265R_TB_CBF | P265R_TB_PCM)) {
-                const int cls = tb_class(tb);
-                const size_t nn = (size_t)1 << (2 * tb.log2_size);
-                if (sp && cls < RC_NUM) {              // sparse TB: its entries + the index of the first
-                    const uint32_t cnt = tb_sparse_count(pic.tbs[t]);
-                    h_beg[beg_fill[cls]++] = (uint32_t)ent_fill[cls];
-                    if (cnt) std::memcpy(h_ent + ent_fill[cls], sp[i].nz + tb.coef_off, sizeof(uint32_t) * cnt);
-                    ent_fill[cls] += cnt;
-                } else {
-                    int16_t* dst = sp ? h_raw + (pool_fill[cls] - pool_base[RC_RAW]) : h_pool + pool_fill[cls];
-                    const int16_t* src = pic.coef + tb.coef_off;
-                    switch (tb.log2_size) {            // fixed sizes: inlined vector moves, no memcpy call per TB
-                        case 2: std::memcpy(dst, src, 16 * sizeof(int16_t)); break;
-                        case 3: std::memcpy(dst, src, 64 * sizeof(int16_t)); break;
-                        case 4: std::memcpy(dst, src, 256 * sizeof(int16_t)); break;
-                        default: std::memcpy(dst, src, 1024 * sizeof(int16_t)); break;
-                    }
-                }
-                tb.coef_off = (uint32_t)pool_fill[cls];
-                if (cls < RC_NUM) h_jobs[cls][job_fill[cls]++] = ResJob{tb.coef_off, tb.qp, tb.flags, tb.log2_size, tb.c_idx};
-                pool_fill[cls] += nn;
-            }
-            tb_dst[t] = tb;
-        }
-        DevPic& dp = b->h_pics[i];
-        dp.ctus = reinterpret_cast<const p265r_ctu*>(dbase + o_ctus) + (size_t)i * nc;
-        dp.tbs = reinterpret_cast<const p265r_tb*>(dbase + o_tbs) + tb_at[i];
-        dp.jobs = reinterpret_cast<IntraJob*>(dbase + o_ijobs) + tb_at[i];
-        dp.jcount = reinterpret_cast<uint32_t*>(dbase + o_jcount) + 4 * (size_t)i * nc;
-        unsigned char* rec = dbase + o_rec + pic_plane_bytes * i;
-        dp.rec[0] = rec;
-        dp.rec[1] = rec + align_up(plane_bytes[0], 256);
-        dp.rec[2] = dp.rec[1] + align_up(plane_bytes[1], 256);
-        dp.dbk_map = dbk ? dbase + o_map + map_bytes * i : nullptr;
-        dp.pool_rel = -(int32_t)((o_res - o_pool) / sizeof(int16_t));
-        dp.zero_off = (uint32_t)pool_total;
-        dp.wh = (uint32_t)psize[i][0] | (uint32_t)psize[i][1] << 16;
-        dp.pad_ = 0;
-        if (lf) {
-            unsigned char* o = dbase + o_out + pic_plane_bytes * i;
-            dp.out[0] = o;
-            dp.out[1] = o + align_up(plane_bytes[0], 256);
-            dp.out[2] = dp.out[1] + align_up(plane_bytes[1], 256);
-        } else {
-            for (int c = 0; c < 3; ++c) dp.out[c] = dp.rec[c];
-        }
-        if (pic.nofilter) {
-            std::memcpy(host + s_nf + nf_at[i] * nf_bytes, pic.nofilter, pnf[i]);   // (slot of the context size)
-            dp.nofilter = dbase + o_nf + nf_at[i] * nf_bytes;
-        } else {
-            dp.nofilter = nullptr;
-        }
-        };
-    // Packing and H2D overlap: the pictures go in chunks; a chunk's ranges of every array (CTU and TB
-    // records, each class slab of the coefficient pool, each residual job list, no-filter maps) are
-    // enqueued as soon as the chunk is packed, so the DMA engine copies chunk k while the host packs
-    // chunk k + 1 (the staging ranges of different chunks are disjoint).  The DevPic table and the
-    // error word follow last; the gaps between the arrays are zeroed on the device.
-    (void)hipSetDevice(ctx->device);
-    if (P265R_UP_STREAM == 2 && !ctx->up_stream && e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking);
-    hipStream_t st = P265R_UP_STREAM ? ctx->up_stream : b->stream;
-    auto h2d_to = [&](void* dst, size_t host_off, size_t bytes) {
-        if (e == hipSuccess && bytes) {
-            e = hipMemcpyAsync(dst, host + host_off, bytes, hipMemcpyHostToDevice, st);
-            b->h2d_bytes += bytes;
-        }
+
+    // Packing and H2D overlap: the pictures go in chunks, and a chunk's copies (UploadPlan::chunk_copies) are
+    // enqueued as soon as it is packed, so the DMA engine copies chunk k while the host packs chunk k + 1.
+    // The DevPic table and the error word follow last; the gaps between the arrays are zeroed on the device.
+    hipError_t e = hipSuccess;
+    hipStream_t st = b->stream;
+    unsigned char* d_sp = static_cast<unsigned char*>(ctx->sp_mem);
+    auto h2d = [&](const H2dCopy& c) {
+        if (e != hipSuccess) return;
+        e = hipMemcpyAsync((c.to_landing ? d_sp : dbase) + c.dst_off, host + c.host_off, c.bytes, hipMemcpyHostToDevice, st);
+        b->h2d_bytes += c.bytes;
     };
-    auto h2d = [&](size_t dev_off, size_t host_off, size_t bytes) { h2d_to(dbase + dev_off, host_off, bytes); };
-    if (e == hipSuccess) e = hipMemsetAsync(dbase + o_res, 0, o_ijobs - o_res, st);   // residual pool, job lists
-    if (e == hipSuccess) e = hipMemsetAsync(dbase + o_ijobs, 0, o_rec - o_ijobs, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dbase + plan.o_res, 0, plan.o_ijobs - plan.o_res, st);   // residual pool, job lists
+    if (e == hipSuccess) e = hipMemsetAsync(dbase + plan.o_ijobs, 0, plan.o_rec - plan.o_ijobs, st);
     // sparse: the expand kernels of a chunk follow its copies -- on the same stream, or (P265R_EXPAND_STREAM) on
     // a second one behind an event, beside the next chunk's copies; with timing on, an event pair per chunk
-    unsigned char* d_sp = static_cast<unsigned char*>(ctx->sp_mem);
     const uint32_t* d_ent = reinterpret_cast<const uint32_t*>(d_sp);
-    const uint32_t* d_beg = sp ? reinterpret_cast<const uint32_t*>(d_sp + (s_beg - s_ent)) : nullptr;
+    const uint32_t* d_beg = sp ? reinterpret_cast<const uint32_t*>(d_sp + (plan.s_beg - plan.s_ent)) : nullptr;
     hipStream_t xs = st;
     const bool time_expand = sp && ctx->timing;
     enum { EV_JOIN = 16, EV_TIMED = 17, EV_NUM = 17 + 32 };      // [k]: chunk k's gate; [EV_TIMED + 2 k (+ 1)]: its timed pair
@@ -1122,29 +812,12 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
         if (ctx->exp_stream) xs = ctx->exp_stream;
     }
     ctx->last_expand_ms = -1.0;
-    for (int k = 0; k < n_chunks; ++k) {
-        const int p0 = chunk_lo(k), p1 = chunk_lo(k + 1);
-        parallel_for(p1 - p0, [&](int j) { pack_pic(p0 + j); });
-        h2d(o_ctus + sizeof(p265r_ctu) * nc * (size_t)p0, o_ctus + sizeof(p265r_ctu) * nc * (size_t)p0,
-            sizeof(p265r_ctu) * nc * (size_t)(p1 - p0));
-        const size_t t1 = p1 < n_pics ? tb_at[p1] : n_tbs_total;
-        h2d(o_tbs + sizeof(p265r_tb) * tb_at[p0], o_tbs + sizeof(p265r_tb) * tb_at[p0], sizeof(p265r_tb) * (t1 - tb_at[p0]));
-        for (int c = sp ? (int)RC_RAW : 0; c < N_POOLS; ++c) {
-            const size_t q0 = pool_at[p0][c], q1 = p1 < n_pics ? pool_at[p1][c] : pool_base[c] + pool_sz[c];
-            h2d(o_pool + sizeof(int16_t) * q0, o_pool + sizeof(int16_t) * (sp ? q0 - pool_base[RC_RAW] : q0), sizeof(int16_t) * (q1 - q0));
-        }
-        for (int c = 0; c < RC_NUM; ++c) {
-            const size_t j0 = (size_t)job_at[p0][c], j1 = p1 < n_pics ? (size_t)job_at[p1][c] : (size_t)n_jobs[c];
-            h2d(o_jobs[c] + sizeof(ResJob) * j0, s_jobs + (o_jobs[c] - o_jobs[0]) + sizeof(ResJob) * j0, sizeof(ResJob) * (j1 - j0));
-        }
-        const size_t f1 = p1 < n_pics ? nf_at[p1] : n_nf;
-        h2d(o_nf + nf_bytes * nf_at[p0], s_nf + nf_bytes * nf_at[p0], nf_bytes * (f1 - nf_at[p0]));
+    for (int k = 0; k < plan.n_chunks; ++k) {
+        const int p0 = plan.chunk_lo(k), p1 = plan.chunk_lo(k + 1);
+        parallel_for(p1 - p0, [&](int j) { pack_picture(plan, p0 + j, pics, sp, host, dbase, &b->h_pics[p0 + j]); });
+        if (sp) close_chunk(plan, k, host);
+        for (const H2dCopy& c : plan.chunk_copies(k)) h2d(c);
         if (!sp) continue;
-        // the chunk's entries and begin words (each class range closed by the index past its last entry)
-        for (int c = 0; c < RC_NUM; ++c) h_beg[beg_kc[k * RC_NUM + c + 1] - 1] = (uint32_t)ent_kc[k * RC_NUM + c + 1];
-        const size_t e0 = ent_kc[k * RC_NUM], e1 = ent_kc[(k + 1) * RC_NUM], b0 = beg_kc[k * RC_NUM], b1 = beg_kc[(k + 1) * RC_NUM];
-        h2d_to(d_sp + sizeof(uint32_t) * e0, s_ent + sizeof(uint32_t) * e0, sizeof(uint32_t) * (e1 - e0));
-        h2d_to(d_sp + (s_beg - s_ent) + sizeof(uint32_t) * b0, s_beg + sizeof(uint32_t) * b0, sizeof(uint32_t) * (b1 - b0));
         if (xs != st) {
             hipEvent_t gate = expand_event(k);
             if (e == hipSuccess) e = hipEventRecord(gate, st);
@@ -1152,40 +825,12 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
         }
         if (time_expand) { hipEvent_t t0 = expand_event(EV_TIMED + 2 * k); if (e == hipSuccess) e = hipEventRecord(t0, xs); }
         for (int c = 0; c < RC_NUM && e == hipSuccess; ++c) {
-            const size_t j0 = (size_t)job_at[p0][c], j1 = p1 < n_pics ? (size_t)job_at[p1][c] : (size_t)n_jobs[c];
-            const int nj = (int)(j1 - j0);
-            if (!nj) continue;
-            const uint32_t* beg = d_beg + beg_kc[k * RC_NUM + c];
-            const ResJob* jobs = b->d_jobs[c] + j0;
-            const size_t q0 = pool_at[p0][c];                    // = the slab offset of job j0
-#if P265R_EXPAND_SCATTER
-            const size_t q1 = p1 < n_pics ? pool_at[p1][c] : pool_base[c] + pool_sz[c];
-            e = hipMemsetAsync(b->d_pool + q0, 0, sizeof(int16_t) * (q1 - q0), xs);
-            if (e != hipSuccess) break;
-            switch (c) {
-                case RC_DST4: case RC_DCT4: case RC_TSKIP: coef_scatter_kernel<1><<<(nj + 255) / 256, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
-                case RC_DCT8: coef_scatter_kernel<4><<<(nj + 63) / 64, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
-                case RC_DCT16: coef_scatter_kernel<16><<<(nj + 15) / 16, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
-                default: coef_scatter_kernel<64><<<(nj + 3) / 4, 256, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
-            }
-#else
-            const int per_block = kExpandWaves * kExpandTile;    // int16 per block of a fixed-size class
-            switch (c) {
-                case RC_DST4: case RC_DCT4:
-                    coef_expand_kernel<2><<<(unsigned)(((size_t)nj * 16 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
-                case RC_DCT8:
-                    coef_expand_kernel<3><<<(unsigned)(((size_t)nj * 64 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
-                case RC_DCT16:
-                    coef_expand_kernel<4><<<(unsigned)(((size_t)nj * 256 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
-                case RC_DCT32:
-                    coef_expand_kernel<5><<<(unsigned)(((size_t)nj * 1024 + per_block - 1) / per_block), 64 * kExpandWaves, 0, xs>>>(b->d_pool, q0, beg, d_ent, nj); break;
-                default:
-                    coef_expand_jobs_kernel<<<(unsigned)((nj + kExpandWaves - 1) / kExpandWaves), 64 * kExpandWaves, 0, xs>>>(b->d_pool, jobs, beg, d_ent, nj); break;
-            }
-#endif
-            e = hipGetLastError();
+            const size_t j0 = (size_t)plan.job_at[p0][c];
+            const int nj = plan.job_at[p1][c] - plan.job_at[p0][c];
+            if (nj) e = launch_expand(xs, b->d_pool, c, b->d_jobs[c] + j0, nj, plan.pool_at[p0][c], plan.pool_at[p1][c],
+                                      d_beg + plan.beg_kc[k * RC_NUM + c], d_ent);
         }
-        if (time_expand) { hipEvent_t t1e = expand_event(EV_TIMED + 2 * k + 1); if (e == hipSuccess) e = hipEventRecord(t1e, xs); }
+        if (time_expand) { hipEvent_t t1 = expand_event(EV_TIMED + 2 * k + 1); if (e == hipSuccess) e = hipEventRecord(t1, xs); }
     }
     if (xs != st) {                                              // the upload's stream waits for the last expand
         hipEvent_t join = expand_event(EV_JOIN);
@@ -1193,36 +838,21 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
         if (e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
     }
     P265R_UT("pack");
-    std::memcpy(host + o_pics, b->h_pics.data(), sizeof(DevPic) * n_pics);
-    b->view.rec0 = dbase + o_rec;
-    b->view.out0 = lf ? dbase + o_out : dbase + o_rec;
-    b->view.pic_bytes = pic_plane_bytes;
-    b->view.plane_off[0] = 0;
-    b->view.plane_off[1] = align_up(plane_bytes[0], 256);
-    b->view.plane_off[2] = b->view.plane_off[1] + align_up(plane_bytes[1], 256);
-    b->view.ctus0 = reinterpret_cast<const p265r_ctu*>(dbase + o_ctus);
-    b->view.err = b->d_err;
-    std::memset(host + o_err, 0, o_ctus - o_err);                                        // error word
-    std::memset(host + o_pics + sizeof(DevPic) * n_pics, 0, o_err - (o_pics + sizeof(DevPic) * n_pics));
     // alignment gaps between the arrays and the coefficient pool's pad: zero on the device, as the device
     // image always had them; then the DevPic table and the error word (complete before returning: the
     // staging buffer is refilled by the next upload)
-    {
-        const size_t ctus_end = o_ctus + sizeof(p265r_ctu) * nc * (size_t)n_pics;
-        const size_t tbs_end = o_tbs + sizeof(p265r_tb) * n_tbs_total;
-        const size_t pool_end = o_pool + sizeof(int16_t) * pool_total;
-        if (e == hipSuccess && o_tbs > ctus_end) e = hipMemsetAsync(dbase + ctus_end, 0, o_tbs - ctus_end, st);
-        if (e == hipSuccess && o_pool > tbs_end) e = hipMemsetAsync(dbase + tbs_end, 0, o_pool - tbs_end, st);
-        if (e == hipSuccess && o_res > pool_end) e = hipMemsetAsync(dbase + pool_end, 0, o_res - pool_end, st);
-    }
-    h2d(0, 0, o_ctus);
-    if (e == hipSuccess && recon_input) {
+    pack_header(plan, b->h_pics.data(), host);
+    for (const ZeroRange& z : plan.gap_zeros())
+        if (e == hipSuccess && z.bytes) e = hipMemsetAsync(dbase + z.off, 0, z.bytes, st);
+    h2d(plan.header_copy());
+    if (e == hipSuccess && plan.recon_input) {
+        const Geo& g = ctx->geo;
+        const size_t pb = plan.pel_bytes;
         for (int i = 0; i < n_pics && e == hipSuccess; ++i)
             for (int c = 0; c < 3 && e == hipSuccess; ++c) {
-                const int wd[3] = {psize[i][0], psize[i][0] / 2, psize[i][0] / 2}, ht[3] = {psize[i][1], psize[i][1] / 2, psize[i][1] / 2};
-                e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, pics[i].recon[c], wd[c] * pb, wd[c] * pb, ht[c],
-                                     hipMemcpyHostToDevice, st);
-                b->h2d_bytes += (size_t)wd[c] * pb * ht[c];
+                const size_t wd = (size_t)(plan.psize[i][0] >> (c ? 1 : 0)), ht = (size_t)(plan.psize[i][1] >> (c ? 1 : 0));
+                e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, pics[i].recon[c], wd * pb, wd * pb, ht, hipMemcpyHostToDevice, st);
+                b->h2d_bytes += wd * pb * ht;
             }
     }
     P265R_UT("enqueue");
@@ -1230,7 +860,7 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
     P265R_UT("h2d");
     if (time_expand && e == hipSuccess) {
         double ms = 0;
-        for (int k = 0; k < n_chunks && e == hipSuccess; ++k) {
+        for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
             float t = 0;
             e = hipEventElapsedTime(&t, ctx->exp_ev[EV_TIMED + 2 * k], ctx->exp_ev[EV_TIMED + 2 * k + 1]);
             ms += t;
@@ -1246,6 +876,7 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
     }
 #endif
 #undef P265R_UT
+#undef P265R_UT_AT
     if (e != hipSuccess) {
         // copies (and expand kernels) enqueued before the failing call may still be in flight: let them end
         // before the allocation they write is freed

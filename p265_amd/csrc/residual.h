@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "batch_types.h"   // ResJob, ResClass
 #include "tables.h"
 
 namespace p265r {
@@ -26,16 +27,6 @@ __device__ __forceinline__ void res_store16(int16_t* p, uint32_t a, uint32_t b, 
     if constexpr (P265R_RES_NT) __builtin_nontemporal_store(res_u4{a, b, c, d}, reinterpret_cast<res_u4*>(p));
     else *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 }
-
-struct ResJob {          // 8 bytes, one per coded TB, in pool order within its class
-    uint32_t off;        // int16 offset of the TB in the pool
-    uint8_t  qp;         // qP (incl. QpBdOffset)
-    uint8_t  flags;      // P265R_TB_*
-    uint8_t  log2;
-    uint8_t  c_idx;
-};
-
-enum ResClass { RC_DST4 = 0, RC_DCT4, RC_DCT8, RC_DCT16, RC_DCT32, RC_TSKIP, RC_NUM };
 
 __device__ __forceinline__ int clamp16(long long v) {
     return v < -32768 ? -32768 : (v > 32767 ? 32767 : (int)v);

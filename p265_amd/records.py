@@ -258,7 +258,7 @@ def check_shapes(params, pic: Picture):
 
 
 def validate(params, pic: Picture):
-    """Host-side checks mirroring the C++ ones (p265_amd/csrc/p265r.hip: validate_picture).
+    """Host-side checks mirroring the C++ ones (p265_amd/csrc/upload_host.cpp: validate_picture).
 
     The kernels assume every record lies inside its CTU and picture; these checks are
     what keeps a malformed record from faulting the GPU.

@@ -282,6 +282,47 @@ def test_sparse_upload_moves_fewer_bytes(recon_mod):
     assert S <= D - 2 * C_s + 4 * n_nz + 8 * J + 65536
 
 
+def _bytes_case(name):
+    """(params, pictures) of a tiny batch whose upload_bytes are pinned below."""
+    if name == "ragged":
+        big = R.make_params(pic_width=264, pic_height=200, ctb_log2_size=5)
+        pics = []
+        for k, (w, h) in enumerate([(264, 200), (128, 72), (40, 200), (264, 8)]):        # test_ragged_batch's
+            pp = R.pic_params(big, R.Picture(ctus=None, tbs=None, coef=None, size=(w, h)))
+            pic = synth.make_picture(pp, 7350 + k, perf=bool(k % 2), deblocking=True, pcm_rate=0.05, tskip_rate=0.1)
+            pic.size = (w, h)
+            pics.append(pic)
+        return big, pics
+    n, ctb_log2, kw = {"1 x ctb 64": (1, 6, {}),
+                       "16 x ctb 32": (16, 5, dict(pcm_rate=0.1, bypass_rate=0.05, deblocking=True)),    # no-filter maps
+                       "27 x ctb 16": (27, 4, dict(tskip_rate=0.1))}[name]
+    params = R.make_params(pic_width=64, pic_height=64, ctb_log2_size=ctb_log2)
+    return params, [synth.make_picture(params, 7800 + s, perf=bool(s % 2), **kw) for s in range(n)]
+
+
+# p265r_batch_upload_bytes (dense, sparse) of each case, recorded from the library of commit 2a96b6f (before
+# the upload was split into the host planner of upload_host.cpp and the enqueue loop): the count is integer
+# arithmetic over the layout and the chunk copy lists, so any change of either shows here.
+_UPLOAD_BYTES = {"1 x ctb 64": (45304, 39944), "16 x ctb 32": (234288, 165096), "27 x ctb 16": (381704, 254268),
+                 "ragged": (266748, 186868)}
+
+
+@pytest.mark.parametrize("name", list(_UPLOAD_BYTES))
+def test_upload_bytes_are_pinned(recon_mod, name):
+    params, pics = _bytes_case(name)
+    if name == "16 x ctb 32":
+        assert any(p.nofilter is not None for p in pics) and any((p.ctus["flags"] & R.CTU_DEBLOCK).any() for p in pics)
+    got = []
+    with recon_mod.ReconContext(params) as ctx:
+        for sparse in (False, True):
+            b = ctx.upload(pics, sparse=sparse)
+            got.append(ctx.upload_bytes(b))
+            b.free()
+    print("upload bytes %s: dense %d sparse %d" % (name, got[0], got[1]))
+    assert tuple(got) == _UPLOAD_BYTES[name]
+    _digests_equal(recon_mod, params, pics)
+
+
 # ---- 8. end to end ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["synth_main10.bin", "synth_1080p_4pic.bin"])
 def test_decoder_with_sparse_upload(recon_mod, name):
