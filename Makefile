@@ -4,8 +4,9 @@ ARCH ?= gfx950
 # -structurizecfg-skip-uniform-regions: uniform branches stay plain scalar branches (no i1 flow masks in
 # SGPR pairs): row kernel 4.70 -> 4.21 ms per 512 1080p pictures (tools/ab_libs2.sh, round 3)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wall -Wno-unused-function -mllvm -structurizecfg-skip-uniform-regions=true
-# (sparse_host.cpp, upload_host.cpp: the host-only parts of the upload, plain C++ -- see sparse-check, upload-check)
-SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp
+# (sparse_host.cpp, upload_host.cpp: the host-only parts of the upload, plain C++ -- see sparse-check, upload-check;
+# export_host.cpp: the host-only part of the device-side output)
+SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/export_host.cpp
 HDR := $(wildcard p265_amd/csrc/*.h) include/p265r.h
 
 CXX ?= g++
@@ -44,7 +45,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -65,6 +66,14 @@ upload-check: tools/upload_check.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc
 		-o tools/upload_check tools/upload_check.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/sparse_host.cpp
 	./tools/upload_check
 .PHONY: upload-check
+
+# host sanitizer check of the device-side output's host code (descriptor validation, layout, slot checks, RGB
+# coefficients): a stand-alone CPU program, not part of `all`
+export-check: tools/export_check.cpp p265_amd/csrc/export_host.cpp p265_amd/csrc/export_host.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o tools/export_check tools/export_check.cpp p265_amd/csrc/export_host.cpp
+	./tools/export_check
+.PHONY: export-check
 
 # experiment builds: make variant V=name FLAGS="-DX=1"  ->  p265_amd/libp265r_name.so
 variant:

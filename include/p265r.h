@@ -236,6 +236,77 @@ int  p265r_batch_digest_slots(p265r_ctx* ctx, p265r_batch* batch, uint64_t* out,
 int  p265r_batch_job_count(p265r_ctx* ctx, p265r_batch* batch, uint64_t* luma, uint64_t* chroma);
 int  p265r_batch_free(p265r_ctx* ctx, p265r_batch* batch);
 
+/* ---- device-side output: cropped frames in device memory, in the consumer's format ---------------
+ * No counterpart in the reference (which parses the conformance window, sps.py:48-53, and never
+ * applies it).  The arithmetic is fixed: B = BitDepth, crop origin (l, t).
+ *   YUV formats: luma dst = src[t + y][l + x], chroma the same at half the coordinates; MSB16 shifts
+ *     left by 16 - B; semi-planar plane 1 holds Cb at element 2 i and Cr at element 2 i + 1.
+ *   Chroma at luma position (x, y) of the DECODED picture (indices clamped to that picture, not to
+ *     the window): NEAREST C[y >> 1][x >> 1]; BILINEAR first vertically at scale 4, j = y >> 1:
+ *     even y v[i] = C[j - 1][i] + 3 C[j][i], odd y v[i] = 3 C[j][i] + C[j + 1][i]; then, i = x >> 1:
+ *     even x (v[i] + 2) >> 2, odd x (v[i] + v[i + 1] + 4) >> 3.
+ *   RGB: D = 8 for P265R_SMP_U8, else B; y = Y - yoff, cb = Cb - half, cr = Cr - half;
+ *     R = clip((cy y + crr cr + 8192) >> 14), G = clip((cy y - cgb cb - cgr cr + 8192) >> 14),
+ *     B = clip((cy y + cbb cb + 8192) >> 14), int32, arithmetic shift, clip to 0 .. 2^D - 1, with the
+ *     integers of p265r_export_coefficients.  F32 = float(v) * float(1 / (2^B - 1)) (one fp32
+ *     multiply), F16 = that value rounded to nearest even. */
+#define P265R_FMT_PLANAR      0u
+#define P265R_FMT_SEMIPLANAR  1u
+#define P265R_FMT_RGB_PLANAR  2u
+#define P265R_FMT_RGB_PACKED  3u
+#define P265R_SMP_NATIVE      0u
+#define P265R_SMP_MSB16       1u
+#define P265R_SMP_U8          2u
+#define P265R_SMP_F16         3u
+#define P265R_SMP_F32         4u
+#define P265R_MAT_BT601       0u
+#define P265R_MAT_BT709       1u
+#define P265R_MAT_BT2020      2u
+#define P265R_UP_NEAREST      0u
+#define P265R_UP_BILINEAR     1u
+
+typedef struct p265r_export_desc {
+    uint32_t format;     /* P265R_FMT_PLANAR (Y, Cb, Cr planes) | P265R_FMT_SEMIPLANAR (Y, then CbCr
+                            interleaved: NV12 / P010 / P012) | P265R_FMT_RGB_PLANAR (R, G, B planes:
+                            "CHW") | P265R_FMT_RGB_PACKED (RGBRGB...: "HWC")                        */
+    uint32_t sample;     /* P265R_SMP_NATIVE (uint8 at BitDepth 8, uint16 above, LSB-justified) |
+                            P265R_SMP_MSB16 (uint16, v << (16 - BitDepth): P010 / P012; YUV formats
+                            at BitDepth > 8 only) | P265R_SMP_U8 | P265R_SMP_F16 | P265R_SMP_F32
+                            (the last three: RGB formats only)                                      */
+    uint32_t matrix;     /* RGB only: P265R_MAT_BT601 | _BT709 | _BT2020 (non-constant luminance)  */
+    uint32_t full_range; /* RGB only: 0 limited (16..235 / 16..240 scaled to BitDepth), 1 full     */
+    uint32_t upsample;   /* RGB only: P265R_UP_NEAREST | P265R_UP_BILINEAR (chroma sited left /
+                            vertically midway: chroma_sample_loc_type 0)                           */
+    uint16_t crop_left, crop_right, crop_top, crop_bottom;   /* luma samples, even; per picture,
+                            relative to THAT picture's size (ragged batches)                      */
+    uint64_t plane_off[3]; /* byte offset of each destination plane inside a frame slot (semi-planar
+                              uses 2, RGB packed 1); a multiple of the element size                */
+    uint64_t pitch[3];     /* bytes between rows of each destination plane, >= the row's bytes     */
+    uint64_t frame_bytes;  /* bytes between the frame slots of consecutive exported pictures       */
+} p265r_export_desc;
+
+/* host only, no context: fill plane_off / pitch / frame_bytes with the tight layout (planes back to
+ * back, pitch = row bytes) of a w x h picture under desc's format / sample / crop; pitch_align > 1
+ * rounds every pitch and plane offset up to it.  Validates the rest of desc. */
+int  p265r_export_layout(const p265r_params* params, int pic_width, int pic_height,
+                         p265r_export_desc* desc, uint32_t pitch_align);
+/* host only: the eight integers of the RGB conversion, for desc at this bit depth:
+ * {cy, crr, cgb, cgr, cbb, yoff, 1 << (B - 1), D} */
+int  p265r_export_coefficients(const p265r_export_desc* desc, int bit_depth, int32_t out[8]);
+/* enqueue, on the batch's lane and after every run enqueued on it so far, the conversion of pictures
+ * pic_index[0..n) (NULL: all, in order) into frame slots 0..n) of dev_dst; returns without waiting
+ * (p265r_batch_status / p265r_sync wait).  dev_dst is caller-owned device memory on the context's
+ * device.  Everything is checked on the host before a kernel is launched: P265R_EINVAL for an unknown
+ * enum value, a sample type that does not go with the format or bit depth, an odd crop, a crop that
+ * leaves no sample of a listed picture, a pitch below the row bytes or no multiple of the element
+ * size, planes of one slot that overlap, frame_bytes smaller than a slot, a pic_index entry outside
+ * the batch or listed twice, a dev_dst that is not device memory of the context's device;
+ * P265R_ERANGE when n slots do not fit in dst_bytes; P265R_ESTATE for a batch that was never run (a
+ * P265R_PIC_RECON_INPUT batch whose filters never ran: it has no output planes yet).  n <= 65535.
+ * Reads the planes p265r_batch_download returns; one kernel launch, no stream of its own. */
+int  p265r_batch_export(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
+                        void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index, int n);
+
 /* Convenience: upload + run (asynchronous) ... */
 int  p265r_submit(p265r_ctx* ctx, const p265r_picture* pics, int n_pics);
 /* ... then block until outputs are written into the pictures given to submit. */

@@ -68,7 +68,22 @@ class Timings(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
-assert ctypes.sizeof(Params) == 32 and ctypes.sizeof(PictureC) == 104
+class ExportDesc(ctypes.Structure):
+    """p265r_export_desc (device-side output)."""
+    _fields_ = [("format", ctypes.c_uint32), ("sample", ctypes.c_uint32), ("matrix", ctypes.c_uint32),
+                ("full_range", ctypes.c_uint32), ("upsample", ctypes.c_uint32),
+                ("crop_left", ctypes.c_uint16), ("crop_right", ctypes.c_uint16), ("crop_top", ctypes.c_uint16),
+                ("crop_bottom", ctypes.c_uint16), ("plane_off", ctypes.c_uint64 * 3), ("pitch", ctypes.c_uint64 * 3),
+                ("frame_bytes", ctypes.c_uint64)]
+
+
+# p265r_export_desc enums (include/p265r.h)
+FMT_PLANAR, FMT_SEMIPLANAR, FMT_RGB_PLANAR, FMT_RGB_PACKED = 0, 1, 2, 3
+SMP_NATIVE, SMP_MSB16, SMP_U8, SMP_F16, SMP_F32 = 0, 1, 2, 3, 4
+MAT_BT601, MAT_BT709, MAT_BT2020 = 0, 1, 2
+UP_NEAREST, UP_BILINEAR = 0, 1
+
+assert ctypes.sizeof(Params) == 32 and ctypes.sizeof(PictureC) == 104 and ctypes.sizeof(ExportDesc) == 88
 
 # every symbol include/p265r.h declares, with (restype, argtypes)
 _vp = ctypes.c_void_p
@@ -89,6 +104,11 @@ SIGNATURES = {
     "p265r_batch_digest_slots": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "p265r_batch_job_count": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "p265r_batch_free": (ctypes.c_int, [_vp, _vp]),
+    "p265r_export_layout": (ctypes.c_int, [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ExportDesc),
+                                           ctypes.c_uint32]),
+    "p265r_export_coefficients": (ctypes.c_int, [ctypes.POINTER(ExportDesc), ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "p265r_batch_export": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), _vp, ctypes.c_uint64,
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
     "p265r_submit": (ctypes.c_int, [_vp, ctypes.POINTER(PictureC), ctypes.c_int]),
     "p265r_wait": (ctypes.c_int, [_vp]),
     "p265r_sync": (ctypes.c_int, [_vp]),

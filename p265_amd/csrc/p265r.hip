@@ -21,6 +21,8 @@
 
 #include "../../include/p265r.h"
 #include "digest.h"
+#include "export.h"
+#include "export_host.h"
 #include "intra.h"
 #include "intra_prep.h"
 #include "intra_rows.h"
@@ -205,6 +207,8 @@ struct p265r_batch {
     int runs = 0;              // p265r_batch_run calls so far
     hipEvent_t sao_done = nullptr;     // P265R_SAO_AUX: recorded on the aux stream after a run's loop filters
     bool sao_pending = false;          // ... and not yet joined into the lane stream (join_sao)
+    std::vector<void*> exp_idx;        // p265r_batch_export: device copies of the pic_index lists of the exports
+                                       // enqueued since the lane was last synchronised (p265r_batch_status)
     unsigned long long* d_dig = nullptr;   // p265r_batch_digest_async slots: P265R_DIGEST_SLOTS x n_pics x 3
     hipEvent_t intra_done = nullptr;   // recorded after each run's intra phase (the last reader of the
                                        // residual pool and job lists): the next run's residual + prep
@@ -453,6 +457,44 @@ int launch_loop_filters(p265r_ctx* ctx, p265r_batch* b, const Geo& g, hipStream_
         else by_dbk(std::integral_constant<int, 4>{});
     }
     ++*launched;
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// The one launch of p265r_batch_export on stream st: n slots; mw x mh = the largest cropped picture listed.
+template <typename S>
+int launch_export(const p265r_export_desc& d, const DevPic* d_pics, const Geo& g, const ExportArgs& a, int mw, int mh, int n,
+                  hipStream_t st) {
+    const auto grid = [&](int group, int row_units) {
+        return dim3((unsigned)((mw / group + 2 + kExportLanes - 1) / kExportLanes),
+                    (unsigned)((row_units + kExportRows - 1) / kExportRows), (unsigned)n);
+    };
+    if (d.format == P265R_FMT_PLANAR) {
+        export_yuv_kernel<S, false><<<grid(16 / (int)sizeof(S), 2 * mh), 256, 0, st>>>(d_pics, g, a);
+    } else if (d.format == P265R_FMT_SEMIPLANAR) {
+        export_yuv_kernel<S, true><<<grid(16 / (int)sizeof(S), mh + mh / 2), 256, 0, st>>>(d_pics, g, a);
+    } else {
+        const bool bil = d.upsample == P265R_UP_BILINEAR;
+        const int pairs = mh / 2 + (bil ? 1 : 0);
+        auto rgb = [&](auto dtag, auto packed, auto bl) {
+            using D = typename decltype(dtag)::type;
+            constexpr bool PK = decltype(packed)::value, BL = decltype(bl)::value;
+            export_rgb_kernel<S, D, PK, BL><<<grid(sizeof(D) == 1 ? 16 : 8, pairs), 256, 0, st>>>(d_pics, g, a);
+        };
+        auto by_shape = [&](auto dtag) {
+            const bool pk = d.format == P265R_FMT_RGB_PACKED;
+            if (pk && bil) rgb(dtag, std::true_type{}, std::true_type{});
+            else if (pk) rgb(dtag, std::true_type{}, std::false_type{});
+            else if (bil) rgb(dtag, std::false_type{}, std::true_type{});
+            else rgb(dtag, std::false_type{}, std::false_type{});
+        };
+        switch (d.sample) {
+            case P265R_SMP_U8: by_shape(std::enable_if<true, uint8_t>{}); break;
+            case P265R_SMP_F16: by_shape(std::enable_if<true, _Float16>{}); break;
+            case P265R_SMP_F32: by_shape(std::enable_if<true, float>{}); break;
+            default: by_shape(std::enable_if<true, S>{}); break;                  // NATIVE
+        }
+    }
     HIP_TRY(hipGetLastError());
     return P265R_OK;
 }
@@ -1223,6 +1265,8 @@ int p265r_batch_status(p265r_ctx* ctx, p265r_batch* b) {
     HIP_TRY(hipStreamSynchronize(b->stream));
     // the lane is idle now (every run on it, of any batch, has completed)
     ctx->lane_busy &= ~(1u << b->lane);
+    for (void* p : b->exp_idx) (void)hipFree(p);
+    b->exp_idx.clear();
     int err = 0;
     HIP_TRY(hipMemcpy(&err, b->d_err, sizeof(int), hipMemcpyDeviceToHost));
     if (err) {
@@ -1298,6 +1342,71 @@ int p265r_batch_job_count(p265r_ctx* ctx, p265r_batch* b, uint64_t* luma, uint64
     return P265R_OK;
 }
 
+int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* desc, void* dev_dst, uint64_t dst_bytes,
+                       const int32_t* pic_index, int n) {
+    if (!ctx || !b || !desc || !dev_dst) return P265R_EINVAL;
+    if (!pic_index) n = b->n_pics;
+    if (n <= 0 || n > b->n_pics || n > 65535) return P265R_EINVAL;
+    // ---- host checks: nothing is launched unless all of them pass ----------------------------
+    const int B = ctx->params.bit_depth_luma;
+    ExportShape shape;
+    if (const int rc = export_check_desc(*desc, B, &shape)) return rc;
+    std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
+    uint64_t slot_bytes = 0;
+    int mw = 0, mh = 0;
+    for (int i = 0; i < n; ++i) {
+        const int pic = pic_index ? pic_index[i] : i;
+        if (pic < 0 || pic >= b->n_pics) return P265R_EINVAL;
+        if (pic_index) {
+            if (seen[(size_t)pic]) return P265R_EINVAL;
+            seen[(size_t)pic] = 1;
+        }
+        uint64_t sb = 0;
+        if (const int rc = export_check_layout(*desc, shape, b->size[(size_t)pic][0], b->size[(size_t)pic][1], &sb)) return rc;
+        slot_bytes = std::max(slot_bytes, sb);
+        mw = std::max(mw, b->size[(size_t)pic][0] - desc->crop_left - desc->crop_right);
+        mh = std::max(mh, b->size[(size_t)pic][1] - desc->crop_top - desc->crop_bottom);
+    }
+    if ((uint64_t)(uintptr_t)dev_dst % (uint64_t)shape.es) return P265R_EINVAL;
+    const uint64_t need = (uint64_t)(n - 1) * desc->frame_bytes + slot_bytes;
+    if (b->runs == 0) return P265R_ESTATE;                  // (a recon-input batch whose filters never ran: no planes yet)
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the first byte of the destination (and, below, the last) is device memory of this context's device
+    auto on_device = [&](const void* p) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+    };
+    if (!on_device(dev_dst)) return P265R_EINVAL;
+    if (need > dst_bytes) return P265R_ERANGE;
+    if (!on_device(static_cast<const unsigned char*>(dev_dst) + need - 1)) return P265R_EINVAL;
+    // ---- enqueue ---------------------------------------------------------------------------------
+    if (int rc = join_sao(b)) return rc;
+    ExportArgs a{};
+    a.dst = static_cast<uint8_t*>(dev_dst);
+    a.frame_bytes = desc->frame_bytes;
+    for (int k = 0; k < 3; ++k) { a.plane_off[k] = desc->plane_off[k]; a.pitch[k] = desc->pitch[k]; }
+    a.crop_l = desc->crop_left; a.crop_r = desc->crop_right; a.crop_t = desc->crop_top; a.crop_b = desc->crop_bottom;
+    if (shape.rgb) {
+        if (const int rc = export_coefficients(*desc, B, a.coef)) return rc;
+        a.fscale = (float)(1.0 / (double)((1 << B) - 1));
+    }
+    a.shift = desc->sample == P265R_SMP_MSB16 ? 16 - B : 0;
+    if (pic_index) {
+        // the list's device copy lives until the lane is next synchronised (the kernel reads it in stream order)
+        void* d_idx = nullptr;
+        HIP_TRY(hipMalloc(&d_idx, sizeof(int32_t) * (size_t)n));
+        b->exp_idx.push_back(d_idx);
+        HIP_TRY(hipMemcpy(d_idx, pic_index, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        a.pic_index = static_cast<const int32_t*>(d_idx);
+    }
+    const int rc = ctx->geo.pel16 ? launch_export<uint16_t>(*desc, b->d_pics, ctx->geo, a, mw, mh, n, b->stream)
+                                  : launch_export<uint8_t>(*desc, b->d_pics, ctx->geo, a, mw, mh, n, b->stream);
+    if (rc) return rc;
+    ctx->lane_busy |= 1u << b->lane;
+    return P265R_OK;
+}
+
 int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (!ctx || !b) return P265R_EINVAL;
     (void)hipSetDevice(ctx->device);
@@ -1309,6 +1418,7 @@ int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (b->intra_done) (void)hipEventDestroy(b->intra_done);
     if (b->sao_done) (void)hipEventDestroy(b->sao_done);
     if (b->d_dig) (void)hipFree(b->d_dig);
+    for (void* p : b->exp_idx) (void)hipFree(p);
     if (b->mem) {
         // keep the larger of (cache, this allocation) for the next upload (its runs are complete)
         if (!ctx->cache_mem || b->bytes > ctx->cache_bytes) {

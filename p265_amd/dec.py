@@ -6,19 +6,24 @@
 declared but never written, p265:9); ``--skip-syntax-dump`` is accepted for command
 line compatibility (this decoder writes no syntax logs).  Parsing runs on host threads
 (libp265fe.so), reconstruction on the MI355X (libp265r.so); the file is streamed
-(bounded memory) and the YUV written in output order as pictures complete.
+(bounded memory) and the YUV written in output order as pictures complete.  ``--format nv12|p010|rgb24|
+rgb-planar-f16`` (with ``--matrix``, ``--full-range``, ``--upsample`` for RGB) converts on the GPU and writes the
+exported frames; the default ``i420`` is the host path.
 """
 import argparse
 import sys
 import time
 
 from . import decoder
+from . import recon
+
+FORMATS = ("i420", "nv12", "p010", "rgb24", "rgb-planar-f16")
 
 
 def parse_cmd(argv=None):
     ap = argparse.ArgumentParser(prog="p265_amd.dec")
     ap.add_argument("-b", "--bitstream", required=True, help="The h.265 bitstream to be decoded.")
-    ap.add_argument("-o", "--output", help="The reconstructed YUV output (I420, cropped, output order).")
+    ap.add_argument("-o", "--output", help="The reconstructed output (--format, default I420; cropped, output order).")
     ap.add_argument("--skip-syntax-dump", type=int, default=0, help="Accepted for compatibility; no effect.")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="front-end parsing threads (0 = this process's CPU share, <= 16)")
@@ -27,14 +32,28 @@ def parse_cmd(argv=None):
     ap.add_argument("--sparse-upload", action="store_true",
                     help="upload the coefficients as their non-zero levels, expanded on the GPU (same output)")
     ap.add_argument("--no-verify", action="store_true", help="do not fail on a decoded picture hash mismatch")
+    ap.add_argument("--format", choices=FORMATS, default="i420",
+                    help="output format; anything but i420 is converted on the GPU (cropped, device-side output) and "
+                         "copied back once per batch")
+    ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default="bt709", help="RGB formats: the YCbCr matrix")
+    ap.add_argument("--full-range", action="store_true", help="RGB formats: full-range YCbCr (default limited)")
+    ap.add_argument("--upsample", choices=("nearest", "bilinear"), default="nearest", help="RGB formats: chroma upsampling")
     return ap.parse_args(argv)
+
+
+def export_spec(a):
+    """The ExportSpec of the parsed command line; None for the default i420 (the host path, unchanged)."""
+    if a.format == "i420":
+        return None
+    return recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample)
 
 
 def main(argv=None):
     a = parse_cmd(argv)
     t0 = time.time()
     st = decoder.decode_file(a.bitstream, a.output, device=a.device, batch=a.batch, threads=a.threads,
-                             depth=a.depth, verify_hash=not a.no_verify, sparse_upload=a.sparse_upload)
+                             depth=a.depth, verify_hash=not a.no_verify, sparse_upload=a.sparse_upload,
+                             export=export_spec(a))
     dt = time.time() - t0
     print("decoded %d pictures in %.3f s; picture hash SEI checked %d, mismatched %d"
           % (st["pictures"], dt, st["hash_checked"], st["hash_mismatch"]))

@@ -20,6 +20,7 @@ import queue
 import threading
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
+from dataclasses import replace
 from typing import Iterable, Iterator, List, Optional
 
 import numpy as np
@@ -36,6 +37,9 @@ class DecodedFrame:
     planes: list                 # full decoded Y, Cb, Cr (uint8; uint16 above 8 bits), pic_width x pic_height
     crop: tuple                  # (left, right, top, bottom) luma samples
     hash_ok: Optional[bool]      # None: stream carries no picture hash for this picture
+    device: object = None        # export=...: recon.DeviceFrame, this frame cropped and converted in device memory
+                                 # (its batch's buffer is freed when the last frame of the batch is released or
+                                 # collected); planes is then None unless the picture hashes were verified
 
     def cropped(self):
         l, r, t, b = self.crop
@@ -169,7 +173,7 @@ DEFAULT_BATCH, DEFAULT_DEPTH, DEFAULT_CHUNK = 8, 4, 1 << 20
 def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT_BATCH, threads: int = 0,
                   verify_hash: bool = True, min_batch: int = 8, prefetch: int = 4, depth: int = DEFAULT_DEPTH,
                   stats: Optional[StageTimes] = None, cache_contexts: bool = True,
-                  sparse_upload: bool = False) -> Iterator[DecodedFrame]:
+                  sparse_upload: bool = False, export: Optional[recon.ExportSpec] = None) -> Iterator[DecodedFrame]:
     """Decode a stream given as an iterable of byte chunks; yields frames in output order.
 
     Three stages run concurrently: the parse thread (native front-end on its own host threads),
@@ -179,7 +183,10 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     output order).  Batches alternate over ``depth`` back-end contexts, so batch k+1 uploads
     while batch k is downloaded; at most ``depth`` batches are in flight.  Contexts stay warm
     between calls (``cache_contexts``; ``release_contexts()`` frees them).  ``sparse_upload``: the
-    coefficients go up as their non-zero levels (ReconContext.upload(sparse=True)); the output is the same."""
+    coefficients go up as their non-zero levels (ReconContext.upload(sparse=True)); the output is the same.
+    ``export``: every batch is also converted on the device right after its run (ReconContext.export, cropped to
+    each picture's conformance window; the spec's own crop is ignored) and every frame carries its slot as
+    ``DecodedFrame.device``; the planes come back to the host only while ``verify_hash`` is on."""
     import time
     clock = time.perf_counter
     if not threads:
@@ -245,6 +252,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             b = lane.ctx.upload([d.picture for d in group], sparse=sparse_upload)     # records -> HBM
             t1 = clock()
             lane.ctx.run(b)                                     # enqueued; decodes meanwhile
+            if export is not None:                              # ... and converts, behind the run on its lane
+                b.device_frames = lane.ctx.export(b, replace(export, crop=tuple(int(v) for v in group[0].crop)))
         st.add("upload", t1 - t0)
         st.add("run_enqueue", clock() - t1)
         done_q.put((lane, b, group))
@@ -261,7 +270,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
                 end = item is None
                 for d in item or []:
                     if pending and (len(pending) >= batch or
-                                    _param_key(d.params, d.scaling) != _param_key(pending[0].params, pending[0].scaling)):
+                                    _param_key(d.params, d.scaling) != _param_key(pending[0].params, pending[0].scaling) or
+                                    (export is not None and tuple(d.crop) != tuple(pending[0].crop))):
                         submit(pending)
                         pending = []
                     pending.append(d)
@@ -287,8 +297,16 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
         try:
             with lane.lock:
                 t0 = clock()
+                frames = getattr(b, "device_frames", None)
+                need_planes = frames is None or (verify_hash and any(d.hash is not None for d in group))
                 try:
-                    outs = lane.ctx.download(b)                 # waits for the batch, planes -> host
+                    if need_planes:
+                        outs = lane.ctx.download(b)             # waits for the batch, planes -> host
+                    else:
+                        lane.ctx.status(b)                      # waits for the batch; the frames stay on the device
+                        outs = [None] * len(group)
+                    if frames is not None:
+                        frames.detach()                         # complete: it outlives the batch
                 except BaseException:
                     lane.failed = True                          # closed at the end, never cached
                     raise
@@ -298,11 +316,12 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
         finally:
             slots.release()
         ready = []
-        for d, planes in zip(group, outs):
+        for k, (d, planes) in enumerate(zip(group, outs)):
             fr = DecodedFrame(poc=d.poc, output_rank=-1, decode_index=int(d.picture.meta["decode_index"]),
-                              planes=planes, crop=tuple(int(v) for v in d.crop), hash_ok=None)
+                              planes=planes, crop=tuple(int(v) for v in d.crop), hash_ok=None,
+                              device=frames.slot(k) if frames is not None else None)
             futs = None
-            if d.hash is not None:
+            if d.hash is not None and planes is not None:
                 futs = [pool.submit(bitstream.plane_hash, planes[c], d.hash_type) for c in range(3)]
             ready += outq.push((fr, d, futs), d.cvs_id, d.poc, d.max_num_reorder, d.output_flag)
         return ready
@@ -384,7 +403,8 @@ def _file_chunks(path, chunk):
 
 
 def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CHUNK, **kw) -> dict:
-    """Stream a bitstream file to a cropped I420 YUV file in output order; returns counts."""
+    """Stream a bitstream file to a cropped I420 YUV file in output order; returns counts.  With ``export=`` the
+    file holds the exported frames instead (one device-to-host copy per batch, no host crop or interleave)."""
     n = checked = bad = 0
     f = open(output, "wb") if output else None
     try:
@@ -393,9 +413,13 @@ def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CH
             if fr.hash_ok is not None:
                 checked += 1
                 bad += int(not fr.hash_ok)
-            if f:
+            if f and fr.device is not None:
+                f.write(fr.device.tobytes())
+            elif f:
                 for p in fr.cropped():
                     f.write(np.ascontiguousarray(p).tobytes())
+            if fr.device is not None:
+                fr.device.release()
     finally:
         if f:
             f.close()

@@ -13,6 +13,7 @@ or, keeping inputs resident in HBM (the benchmark path):
 Errors raise ``P265RError`` (negative C return codes); there is no CPU fallback.
 """
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -84,9 +85,217 @@ class DecodedPicture:
         return self._at(self.planes, x, y, c_idx)
 
 
+# ---- device-side output (p265r_batch_export) ------------------------------------------------------
+_FORMATS = {"planar": _lib.FMT_PLANAR, "semiplanar": _lib.FMT_SEMIPLANAR, "rgb_planar": _lib.FMT_RGB_PLANAR,
+            "rgb_packed": _lib.FMT_RGB_PACKED}
+_SAMPLES = {"native": _lib.SMP_NATIVE, "msb16": _lib.SMP_MSB16, "u8": _lib.SMP_U8, "f16": _lib.SMP_F16,
+            "f32": _lib.SMP_F32}
+_MATRICES = {"bt601": _lib.MAT_BT601, "bt709": _lib.MAT_BT709, "bt2020": _lib.MAT_BT2020}
+_UPSAMPLES = {"nearest": _lib.UP_NEAREST, "bilinear": _lib.UP_BILINEAR}
+
+
+@dataclass(frozen=True)
+class ExportSpec:
+    """What p265r_batch_export writes: ``format`` planar | semiplanar | rgb_planar | rgb_packed, ``sample``
+    native | msb16 | u8 | f16 | f32, and for RGB ``matrix`` bt601 | bt709 | bt2020, ``full_range`` and
+    ``upsample`` nearest | bilinear (names, or the P265R_* integers).  ``crop`` = (left, right, top, bottom)
+    in luma samples, relative to each picture's own size; ``pitch_align`` > 1 rounds every pitch and plane
+    offset up to it."""
+    format: object = "planar"
+    sample: object = "native"
+    matrix: object = "bt709"
+    full_range: bool = False
+    upsample: object = "nearest"
+    crop: tuple = (0, 0, 0, 0)
+    pitch_align: int = 1
+
+    @staticmethod
+    def named(name, **kw):
+        """The command line's format names: i420 (planar, native), nv12 (semi-planar, native), p010 (semi-planar,
+        MSB-justified 16 bit), rgb24 (packed uint8), rgb-planar-f16."""
+        table = {"i420": ("planar", "native"), "nv12": ("semiplanar", "native"), "p010": ("semiplanar", "msb16"),
+                 "rgb24": ("rgb_packed", "u8"), "rgb-planar-f16": ("rgb_planar", "f16")}
+        if name not in table:
+            raise ValueError("unknown output format %r" % (name,))
+        return ExportSpec(format=table[name][0], sample=table[name][1], **kw)
+
+    def desc(self):
+        """The p265r_export_desc of this spec, layout fields zero."""
+        def enum(v, names, what):
+            if isinstance(v, str):
+                if v not in names:
+                    raise ValueError("unknown %s %r" % (what, v))
+                return names[v]
+            return int(v)
+        d = _lib.ExportDesc()
+        d.format, d.sample = enum(self.format, _FORMATS, "format"), enum(self.sample, _SAMPLES, "sample")
+        d.matrix, d.upsample = enum(self.matrix, _MATRICES, "matrix"), enum(self.upsample, _UPSAMPLES, "upsample")
+        d.full_range = int(self.full_range)
+        d.crop_left, d.crop_right, d.crop_top, d.crop_bottom = (int(v) for v in self.crop)
+        return d
+
+
+class ExportLayout:
+    """A filled p265r_export_desc plus what Python needs to view a frame slot: the element dtype and, per
+    picture size, the shape and byte strides of every destination plane."""
+
+    def __init__(self, desc, bit_depth):
+        self.desc = desc
+        native = np.dtype(np.uint16 if bit_depth > 8 else np.uint8)
+        self.dtype = {_lib.SMP_NATIVE: native, _lib.SMP_MSB16: np.dtype(np.uint16), _lib.SMP_U8: np.dtype(np.uint8),
+                      _lib.SMP_F16: np.dtype(np.float16), _lib.SMP_F32: np.dtype(np.float32)}[desc.sample]
+        self.n_planes = {_lib.FMT_PLANAR: 3, _lib.FMT_SEMIPLANAR: 2, _lib.FMT_RGB_PLANAR: 3, _lib.FMT_RGB_PACKED: 1}[desc.format]
+        self.plane_off = [int(desc.plane_off[k]) for k in range(self.n_planes)]
+        self.pitch = [int(desc.pitch[k]) for k in range(self.n_planes)]
+        self.frame_bytes = int(desc.frame_bytes)
+        self.crop = (desc.crop_left, desc.crop_right, desc.crop_top, desc.crop_bottom)
+
+    def plane_view(self, k, size):
+        """(shape, byte strides) of plane ``k`` of a picture of luma ``size`` = (width, height) before the crop."""
+        l, r, t, b = self.crop
+        w, h = int(size[0]) - l - r, int(size[1]) - t - b
+        es, f = self.dtype.itemsize, self.desc.format
+        if f == _lib.FMT_RGB_PACKED:
+            return (h, w, 3), (self.pitch[0], 3 * es, es)
+        if f == _lib.FMT_SEMIPLANAR and k == 1:
+            return (h // 2, w // 2, 2), (self.pitch[1], 2 * es, es)
+        if f == _lib.FMT_PLANAR and k > 0:
+            return (h // 2, w // 2), (self.pitch[k], es)
+        return (h, w), (self.pitch[k], es)
+
+
+def export_layout(params, spec, size=None):
+    """ExportLayout of ``spec`` for pictures of ``size`` = (width, height) (default: the params' size), through
+    the C p265r_export_layout (host only: no context, no device)."""
+    d = spec.desc()
+    pc = _params_c(params)
+    w, h = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    _lib.check(_lib.load().p265r_export_layout(ctypes.byref(pc), w, h, ctypes.byref(d), int(spec.pitch_align)),
+               "p265r_export_layout")
+    return ExportLayout(d, int(params["bit_depth_luma"]))
+
+
+def export_coefficients(spec, bit_depth):
+    """The eight integers of the RGB conversion (p265r_export_coefficients, host only)."""
+    d = spec.desc()
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.load().p265r_export_coefficients(ctypes.byref(d), int(bit_depth), out), "p265r_export_coefficients")
+    return [int(v) for v in out]
+
+
+class DevicePlane:
+    """One plane of one exported frame in device memory: a version-3 ``__cuda_array_interface__`` that array
+    libraries on the same GPU wrap without a copy.  The memory belongs to the DeviceFrames it came from."""
+
+    def __init__(self, owner, ptr, shape, strides, dtype):
+        self.owner, self.ptr, self.shape, self.strides, self.dtype = owner, int(ptr), tuple(shape), tuple(strides), dtype
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "strides": self.strides,
+                "version": 3}
+
+
+class DeviceFrames:
+    """The frame slots an export wrote (or will have written once its batch's lane is idle): ``ptr`` /
+    ``nbytes`` of the whole buffer, ``layout``, ``sizes`` = the uncropped luma size of the picture in each slot.
+    ``plane(i, k)`` views plane ``k`` of slot ``i`` on the device, ``to_host()`` copies everything back once."""
+
+    def __init__(self, ptr, nbytes, layout, sizes, buffer=None, ctx=None, batch=None):
+        self.ptr, self.nbytes, self.layout, self.sizes = int(ptr), int(nbytes), layout, [tuple(s) for s in sizes]
+        self._buffer, self._ctx, self._batch = buffer, ctx, batch
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def plane(self, i, k):
+        if not 0 <= i < len(self.sizes) or not 0 <= k < self.layout.n_planes:
+            raise IndexError("slot %d plane %d" % (i, k))
+        shape, strides = self.layout.plane_view(k, self.sizes[i])
+        return DevicePlane(self, self.ptr + i * self.layout.frame_bytes + self.layout.plane_off[k], shape, strides,
+                           self.layout.dtype)
+
+    def _download(self):
+        from . import hip
+        if self._ctx is not None:
+            self._ctx.status(self._batch)
+        host = np.empty(self.nbytes, np.uint8)
+        hip.check(hip.lib().hipMemcpy(host.ctypes.data, ctypes.c_void_p(self.ptr), self.nbytes, hip.D2H), "hipMemcpy D2H")
+        return host
+
+    def to_host(self):
+        """Wait for the batch, copy the buffer back in one piece; -> per slot a list of numpy views of its planes."""
+        return self.host_views(self._download())
+
+    def host_views(self, host):
+        """numpy views per slot and plane of a host copy of the buffer (uint8, ``nbytes`` long)."""
+        out = []
+        for i, size in enumerate(self.sizes):
+            planes = []
+            for k in range(self.layout.n_planes):
+                shape, strides = self.layout.plane_view(k, size)
+                planes.append(np.ndarray(shape, self.layout.dtype, host, i * self.layout.frame_bytes + self.layout.plane_off[k],
+                                         strides))
+            out.append(planes)
+        return out
+
+    def detach(self):
+        """The batch is complete (and may be freed): nothing left to wait for."""
+        self._ctx = self._batch = None
+
+    def host(self):
+        """A host copy of the whole buffer, made once (one D2H copy) and kept with this object."""
+        if getattr(self, "_host", None) is None:
+            self._host = self._download()
+        return self._host
+
+    def slot(self, i):
+        """DeviceFrame view of slot ``i`` (keeps this buffer alive)."""
+        return DeviceFrame(self, i)
+
+    def free(self):
+        """Free the buffer if this object allocated it (a caller's ``dst`` stays the caller's)."""
+        if self._buffer is not None:
+            if self._ctx is not None and self._batch is not None and self._batch.handle and self._ctx.handle:
+                self._ctx.status(self._batch)          # the export may still be writing it
+            self._buffer.free()
+            self._buffer = None
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceFrame:
+    """One exported frame: slot ``index`` of a DeviceFrames, which stays allocated while any of its slot views
+    lives (``release()`` drops this one's hold)."""
+
+    def __init__(self, frames, index):
+        self.frames, self.index = frames, int(index)
+
+    @property
+    def planes(self):
+        return [self.frames.plane(self.index, k) for k in range(self.frames.layout.n_planes)]
+
+    def to_host(self):
+        """numpy views of this frame's planes in the buffer's host copy (DeviceFrames.host: one copy per batch)."""
+        return self.frames.host_views(self.frames.host())[self.index]
+
+    def tobytes(self):
+        """The frame's planes back to back, rows tight: what a raw video file holds."""
+        return b"".join(np.ascontiguousarray(p).tobytes() for p in self.to_host())
+
+    def release(self):
+        self.frames = None
+
+
 class Batch:
     def __init__(self, ctx, handle, pics, keep):
         self.ctx, self.handle, self.pics, self._keep = ctx, handle, pics, keep
+        self.device_frames = None            # decoder: the DeviceFrames exported from this batch
 
     def free(self):
         if self.handle:
@@ -287,6 +496,49 @@ class ReconContext:
         _lib.check(self.lib.p265r_batch_job_count(self.handle, batch.handle, ctypes.byref(lu), ctypes.byref(ch)),
                    "p265r_batch_job_count")
         return int(lu.value), int(ch.value)
+
+    # ---- device-side output -----------------------------------------------------------
+    def export_layout(self, spec, pic=None):
+        """ExportLayout of ``spec`` for a picture (a records Picture, a (width, height) pair, or None = the
+        context's size; a ragged batch shares the layout of its largest picture)."""
+        size = None
+        if pic is not None:
+            pp = R.pic_params(self.params, pic) if hasattr(pic, "ctus") else None
+            size = (int(pp["pic_width"]), int(pp["pic_height"])) if pp is not None else (int(pic[0]), int(pic[1]))
+        return export_layout(self.params, spec, size)
+
+    def export(self, batch, spec, dst=None, dst_bytes=None, only=None):
+        """Enqueue, after the batch's runs, the conversion of its pictures (``only``: these, in this order) into
+        frame slots in device memory (p265r_batch_export) and return at once -> DeviceFrames.  ``dst`` None:
+        the buffer is allocated here (hipMalloc) and owned by the result; an integer device address (with
+        ``dst_bytes``): the caller's memory on this context's device, e.g. ``tensor.data_ptr()``.  The slots have
+        the tight (or ``pitch_align``) layout of the context's picture size."""
+        from . import hip
+        lay = self.export_layout(spec)
+        idx = list(range(len(batch.pics))) if only is None else [int(i) for i in only]
+        sizes = []
+        for i in idx:
+            if not 0 <= i < len(batch.pics):
+                raise _lib.P265RError(_lib.EINVAL, "p265r_batch_export")
+            pp = R.pic_params(self.params, batch.pics[i])
+            sizes.append((int(pp["pic_width"]), int(pp["pic_height"])))
+        buf = None
+        if dst is None:
+            hip.set_device(self.device)
+            dst_bytes = lay.frame_bytes * len(idx)
+            buf = hip.DeviceBuffer(dst_bytes)
+            dst = buf.ptr.value
+        elif dst_bytes is None:
+            raise ValueError("dst_bytes: the size of the caller's buffer")
+        arr = (ctypes.c_int32 * len(idx))(*idx) if only is not None else None
+        try:
+            _lib.check(self.lib.p265r_batch_export(self.handle, batch.handle, ctypes.byref(lay.desc), ctypes.c_void_p(int(dst)),
+                                                   int(dst_bytes), arr, len(idx)), "p265r_batch_export")
+        except BaseException:
+            if buf is not None:
+                buf.free()
+            raise
+        return DeviceFrames(dst, dst_bytes, lay, sizes, buffer=buf, ctx=self, batch=batch)
 
     def sync(self):
         _lib.check(self.lib.p265r_sync(self.handle), "p265r_sync")
