@@ -5,8 +5,9 @@ ARCH ?= gfx950
 # SGPR pairs): row kernel 4.70 -> 4.21 ms per 512 1080p pictures (tools/ab_libs2.sh, round 3)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wall -Wno-unused-function -mllvm -structurizecfg-skip-uniform-regions=true
 # (sparse_host.cpp, upload_host.cpp: the host-only parts of the upload, plain C++ -- see sparse-check, upload-check;
-# export_host.cpp: the host-only part of the device-side output)
-SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/export_host.cpp
+# export_host.cpp: the host-only part of the device-side output; pichash_host.cpp: the picture hash of a host plane)
+SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/export_host.cpp \
+       p265_amd/csrc/pichash_host.cpp
 HDR := $(wildcard p265_amd/csrc/*.h) include/p265r.h
 
 CXX ?= g++
@@ -45,7 +46,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -74,6 +75,15 @@ export-check: tools/export_check.cpp p265_amd/csrc/export_host.cpp p265_amd/csrc
 		-o tools/export_check tools/export_check.cpp p265_amd/csrc/export_host.cpp
 	./tools/export_check
 .PHONY: export-check
+
+# host sanitizer check of the picture hash arithmetic (pichash_math.h through p265r_plane_hash_host: RFC 1321's
+# vectors, the CRC and checksum split forms against restatements of D.3.19, rejection codes): a stand-alone CPU
+# program, not part of `all`
+hash-check: tools/hash_check.cpp p265_amd/csrc/pichash_host.cpp p265_amd/csrc/pichash_math.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o tools/hash_check tools/hash_check.cpp p265_amd/csrc/pichash_host.cpp
+	./tools/hash_check
+.PHONY: hash-check
 
 # experiment builds: make variant V=name FLAGS="-DX=1"  ->  p265_amd/libp265r_name.so
 variant:

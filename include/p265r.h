@@ -307,6 +307,33 @@ int  p265r_export_coefficients(const p265r_export_desc* desc, int bit_depth, int
 int  p265r_batch_export(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
                         void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index, int n);
 
+/* ---- device-side picture hash: the decoded_picture_hash SEI values (D.3.19) computed in device memory ----
+ * No counterpart in the reference (no SEI support, nalu.py:130-131).  The hash of a plane runs over its
+ * pictureData: the samples of the picture's OWN size (uncropped) in raster order, one byte per sample at
+ * BitDepth 8, two (little-endian) above.  The 16 bytes per plane have the form the SEI carries (and
+ * p265fe_plane_hash writes): MD5 16 bytes; CRC 2 bytes big-endian, the rest 0; checksum 4 bytes big-endian,
+ * the rest 0.  The values equal P265FE_HASH_*. */
+#define P265R_HASH_MD5      0
+#define P265R_HASH_CRC      1
+#define P265R_HASH_CHECKSUM 2
+/* enqueue, on the batch's lane and after every run and export enqueued on it so far, the hash of the planes
+ * p265r_batch_download returns, into a per-batch buffer of 16 bytes per plane (allocated at the first call,
+ * freed with the batch; a later call overwrites it); returns without waiting.  P265R_EINVAL for a NULL
+ * pointer or an unknown type, P265R_ESTATE for a batch that was never run; checked before any launch. */
+int  p265r_batch_hash_async(p265r_ctx* ctx, p265r_batch* batch, int hash_type);
+/* wait for the batch's lane and copy the buffer: out[(3 * i + c) * 16 ..], n_bytes = 48 * n_pics
+ * (else P265R_EINVAL); P265R_ESTATE before any p265r_batch_hash_async.  Returns what p265r_batch_status
+ * returns. */
+int  p265r_batch_hash_read(p265r_ctx* ctx, p265r_batch* batch, uint8_t* out, int n_bytes);
+/* host only, no context: the same hash of a host plane of width x height samples of bytes_per_sample (1, 2)
+ * bytes, rows stride_bytes apart, through the arithmetic the kernels use: the message is cut into segments of
+ * seg_words 32-bit words (0: one segment) whose terms are combined last segment first (MD5, a serial chain,
+ * ignores the cut).  P265R_EINVAL: a NULL pointer, a non-positive size, a width or height that is no
+ * multiple of 4, bytes_per_sample not 1 or 2, a stride below the row's bytes, an unknown type, a plane of
+ * 2^29 bytes or more. */
+int  p265r_plane_hash_host(const void* plane, int width, int height, uint64_t stride_bytes,
+                           int bytes_per_sample, int hash_type, uint32_t seg_words, uint8_t out[16]);
+
 /* Convenience: upload + run (asynchronous) ... */
 int  p265r_submit(p265r_ctx* ctx, const p265r_picture* pics, int n_pics);
 /* ... then block until outputs are written into the pictures given to submit. */

@@ -82,6 +82,9 @@ FMT_PLANAR, FMT_SEMIPLANAR, FMT_RGB_PLANAR, FMT_RGB_PACKED = 0, 1, 2, 3
 SMP_NATIVE, SMP_MSB16, SMP_U8, SMP_F16, SMP_F32 = 0, 1, 2, 3, 4
 MAT_BT601, MAT_BT709, MAT_BT2020 = 0, 1, 2
 UP_NEAREST, UP_BILINEAR = 0, 1
+# picture hash types (P265R_HASH_*, equal to P265FE_HASH_*) and the bytes of each the SEI carries
+HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
+HASH_BYTES = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 
 assert ctypes.sizeof(Params) == 32 and ctypes.sizeof(PictureC) == 104 and ctypes.sizeof(ExportDesc) == 88
 
@@ -109,6 +112,10 @@ SIGNATURES = {
     "p265r_export_coefficients": (ctypes.c_int, [ctypes.POINTER(ExportDesc), ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
     "p265r_batch_export": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), _vp, ctypes.c_uint64,
                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    "p265r_batch_hash_async": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "p265r_batch_hash_read": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]),
+    "p265r_plane_hash_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)]),
     "p265r_submit": (ctypes.c_int, [_vp, ctypes.POINTER(PictureC), ctypes.c_int]),
     "p265r_wait": (ctypes.c_int, [_vp]),
     "p265r_sync": (ctypes.c_int, [_vp]),

@@ -28,6 +28,7 @@
 #include "intra_rows.h"
 #include "loopfilter.h"
 #include "loopfilter16.h"
+#include "pichash.h"
 #include "sao16.h"
 #include "residual.h"
 #include "coef_expand.h"
@@ -210,6 +211,8 @@ struct p265r_batch {
     std::vector<void*> exp_idx;        // p265r_batch_export: device copies of the pic_index lists of the exports
                                        // enqueued since the lane was last synchronised (p265r_batch_status)
     unsigned long long* d_dig = nullptr;   // p265r_batch_digest_async slots: P265R_DIGEST_SLOTS x n_pics x 3
+    uint8_t* d_hash = nullptr;         // p265r_batch_hash_async: 16 bytes per plane (the SEI form), then one 32-bit
+                                       // accumulator per plane (checksum, CRC)
     hipEvent_t intra_done = nullptr;   // recorded after each run's intra phase (the last reader of the
                                        // residual pool and job lists): the next run's residual + prep
                                        // phase waits for it instead of for the whole previous run
@@ -1327,6 +1330,43 @@ int p265r_batch_digest_slots(p265r_ctx* ctx, p265r_batch* b, uint64_t* out, int 
     return p265r_batch_status(ctx, b);
 }
 
+int p265r_batch_hash_async(p265r_ctx* ctx, p265r_batch* b, int hash_type) {
+    if (!ctx || !b) return P265R_EINVAL;
+    if (hash_type != P265R_HASH_MD5 && hash_type != P265R_HASH_CRC && hash_type != P265R_HASH_CHECKSUM) return P265R_EINVAL;
+    if (b->runs == 0) return P265R_ESTATE;                  // (no output planes yet, as for p265r_batch_export)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_sao(b)) return rc;
+    const int n_planes = 3 * b->n_pics;
+    const size_t out_bytes = 16 * (size_t)n_planes, acc_bytes = sizeof(uint32_t) * (size_t)n_planes;
+    if (!b->d_hash) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_hash), out_bytes + acc_bytes));
+    uint4* out = reinterpret_cast<uint4*>(b->d_hash);
+    uint32_t* acc = reinterpret_cast<uint32_t*>(b->d_hash + out_bytes);
+    if (hash_type == P265R_HASH_MD5) {
+        hash_md5_kernel<<<dim3((unsigned)((n_planes + 63) / 64)), 64, 0, b->stream>>>(b->d_pics, ctx->geo, b->n_pics, out);
+    } else {
+        HIP_TRY(hipMemsetAsync(acc, 0, acc_bytes, b->stream));
+        const dim3 grid((unsigned)((ctx->geo.h + kHashRows - 1) / kHashRows), 3, (unsigned)b->n_pics);
+        if (hash_type == P265R_HASH_CRC) hash_crc_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, acc);
+        else hash_checksum_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, acc);
+        HIP_TRY(hipGetLastError());
+        hash_final_kernel<<<dim3((unsigned)((n_planes + 63) / 64)), 64, 0, b->stream>>>(
+            b->d_pics, ctx->geo, hash_type == P265R_HASH_CRC ? 1 : 0, n_planes, acc, out);
+    }
+    HIP_TRY(hipGetLastError());
+    ctx->lane_busy |= 1u << b->lane;
+    return P265R_OK;
+}
+
+int p265r_batch_hash_read(p265r_ctx* ctx, p265r_batch* b, uint8_t* out, int n_bytes) {
+    if (!ctx || !b || !out || (long long)n_bytes != 48ll * b->n_pics) return P265R_EINVAL;
+    if (!b->d_hash) return P265R_ESTATE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_sao(b)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, b->d_hash, (size_t)n_bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return p265r_batch_status(ctx, b);
+}
+
 int p265r_batch_job_count(p265r_ctx* ctx, p265r_batch* b, uint64_t* luma, uint64_t* chroma) {
     if (!ctx || !b || !luma || !chroma) return P265R_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1418,6 +1458,7 @@ int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (b->intra_done) (void)hipEventDestroy(b->intra_done);
     if (b->sao_done) (void)hipEventDestroy(b->sao_done);
     if (b->d_dig) (void)hipFree(b->d_dig);
+    if (b->d_hash) (void)hipFree(b->d_hash);
     for (void* p : b->exp_idx) (void)hipFree(p);
     if (b->mem) {
         // keep the larger of (cache, this allocation) for the next upload (its runs are complete)

@@ -8,7 +8,8 @@ line compatibility (this decoder writes no syntax logs).  Parsing runs on host t
 (libp265fe.so), reconstruction on the MI355X (libp265r.so); the file is streamed
 (bounded memory) and the YUV written in output order as pictures complete.  ``--format nv12|p010|rgb24|
 rgb-planar-f16`` (with ``--matrix``, ``--full-range``, ``--upsample`` for RGB) converts on the GPU and writes the
-exported frames; the default ``i420`` is the host path.
+exported frames; the default ``i420`` is the host path.  ``--hash-on device`` checks the decoded picture hash SEI
+on the GPU instead of on downloaded planes.
 """
 import argparse
 import sys
@@ -32,6 +33,9 @@ def parse_cmd(argv=None):
     ap.add_argument("--sparse-upload", action="store_true",
                     help="upload the coefficients as their non-zero levels, expanded on the GPU (same output)")
     ap.add_argument("--no-verify", action="store_true", help="do not fail on a decoded picture hash mismatch")
+    ap.add_argument("--hash-on", choices=("host", "device"), default="host",
+                    help="where the decoded picture hash SEI is checked: on downloaded planes (host) or on the GPU "
+                         "(device: 48 bytes per picture come back; with a GPU --format no plane does)")
     ap.add_argument("--format", choices=FORMATS, default="i420",
                     help="output format; anything but i420 is converted on the GPU (cropped, device-side output) and "
                          "copied back once per batch")
@@ -53,7 +57,7 @@ def main(argv=None):
     t0 = time.time()
     st = decoder.decode_file(a.bitstream, a.output, device=a.device, batch=a.batch, threads=a.threads,
                              depth=a.depth, verify_hash=not a.no_verify, sparse_upload=a.sparse_upload,
-                             export=export_spec(a))
+                             export=export_spec(a), hash_on=a.hash_on)
     dt = time.time() - t0
     print("decoded %d pictures in %.3f s; picture hash SEI checked %d, mismatched %d"
           % (st["pictures"], dt, st["hash_checked"], st["hash_mismatch"]))

@@ -39,7 +39,7 @@ class DecodedFrame:
     hash_ok: Optional[bool]      # None: stream carries no picture hash for this picture
     device: object = None        # export=...: recon.DeviceFrame, this frame cropped and converted in device memory
                                  # (its batch's buffer is freed when the last frame of the batch is released or
-                                 # collected); planes is then None unless the picture hashes were verified
+                                 # collected); planes is then None unless the picture hashes were verified on the host
 
     def cropped(self):
         l, r, t, b = self.crop
@@ -173,7 +173,8 @@ DEFAULT_BATCH, DEFAULT_DEPTH, DEFAULT_CHUNK = 8, 4, 1 << 20
 def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT_BATCH, threads: int = 0,
                   verify_hash: bool = True, min_batch: int = 8, prefetch: int = 4, depth: int = DEFAULT_DEPTH,
                   stats: Optional[StageTimes] = None, cache_contexts: bool = True,
-                  sparse_upload: bool = False, export: Optional[recon.ExportSpec] = None) -> Iterator[DecodedFrame]:
+                  sparse_upload: bool = False, export: Optional[recon.ExportSpec] = None,
+                  hash_on: str = "host") -> Iterator[DecodedFrame]:
     """Decode a stream given as an iterable of byte chunks; yields frames in output order.
 
     Three stages run concurrently: the parse thread (native front-end on its own host threads),
@@ -186,8 +187,15 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     coefficients go up as their non-zero levels (ReconContext.upload(sparse=True)); the output is the same.
     ``export``: every batch is also converted on the device right after its run (ReconContext.export, cropped to
     each picture's conformance window; the spec's own crop is ignored) and every frame carries its slot as
-    ``DecodedFrame.device``; the planes come back to the host only while ``verify_hash`` is on."""
+    ``DecodedFrame.device``; the planes come back to the host only while ``verify_hash`` is on.
+    ``hash_on``: "host" (default) hashes the downloaded planes on the host pool; "device" computes the picture
+    hashes of every batch on the GPU behind its run (ReconContext.hash_async; batches are also cut where the
+    SEI's hash type changes), reads 48 bytes per picture and never hashes on the host: with ``export`` no
+    plane leaves the device.  ``hash_ok`` and HashMismatch mean the same in both."""
     import time
+    if hash_on not in ("host", "device"):
+        raise ValueError("hash_on: 'host' or 'device', not %r" % (hash_on,))
+    device_hash = hash_on == "device"
     clock = time.perf_counter
     if not threads:
         threads = host_threads()
@@ -231,6 +239,9 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     lanes = {}                          # params bytes -> [_Lane] * depth
     k_submit = [0]
 
+    def hash_key(d):
+        return int(d.hash_type) if d.hash is not None else None
+
     def lanes_for(params, scaling):
         key = _param_key(params, scaling)
         ls = lanes.get(key)
@@ -254,6 +265,9 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             lane.ctx.run(b)                                     # enqueued; decodes meanwhile
             if export is not None:                              # ... and converts, behind the run on its lane
                 b.device_frames = lane.ctx.export(b, replace(export, crop=tuple(int(v) for v in group[0].crop)))
+            if device_hash and hash_key(group[0]) is not None:  # ... and hashes its planes where they are
+                lane.ctx.hash_async(b, hash_key(group[0]))
+                b.hash_type = hash_key(group[0])
         st.add("upload", t1 - t0)
         st.add("run_enqueue", clock() - t1)
         done_q.put((lane, b, group))
@@ -271,7 +285,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
                 for d in item or []:
                     if pending and (len(pending) >= batch or
                                     _param_key(d.params, d.scaling) != _param_key(pending[0].params, pending[0].scaling) or
-                                    (export is not None and tuple(d.crop) != tuple(pending[0].crop))):
+                                    (export is not None and tuple(d.crop) != tuple(pending[0].crop)) or
+                                    (device_hash and hash_key(d) != hash_key(pending[0]))):
                         submit(pending)
                         pending = []
                     pending.append(d)
@@ -298,13 +313,17 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             with lane.lock:
                 t0 = clock()
                 frames = getattr(b, "device_frames", None)
-                need_planes = frames is None or (verify_hash and any(d.hash is not None for d in group))
+                hash_type = getattr(b, "hash_type", None)       # hashed on the device (hash_on="device")
+                need_planes = frames is None or (not device_hash and verify_hash and any(d.hash is not None for d in group))
+                hashes = None
                 try:
                     if need_planes:
                         outs = lane.ctx.download(b)             # waits for the batch, planes -> host
                     else:
                         lane.ctx.status(b)                      # waits for the batch; the frames stay on the device
                         outs = [None] * len(group)
+                    if hash_type is not None:
+                        hashes = lane.ctx.hash_read(b)          # 48 bytes per picture
                     if frames is not None:
                         frames.detach()                         # complete: it outlives the batch
                 except BaseException:
@@ -321,7 +340,10 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
                               planes=planes, crop=tuple(int(v) for v in d.crop), hash_ok=None,
                               device=frames.slot(k) if frames is not None else None)
             futs = None
-            if d.hash is not None and planes is not None:
+            if hashes is not None:
+                nb = len(d.hash[0])
+                fr.hash_ok = all(hashes[k, c, :nb].tobytes() == d.hash[c] for c in range(3))
+            elif d.hash is not None and planes is not None and not device_hash:
                 futs = [pool.submit(bitstream.plane_hash, planes[c], d.hash_type) for c in range(3)]
             ready += outq.push((fr, d, futs), d.cvs_id, d.poc, d.max_num_reorder, d.output_flag)
         return ready
@@ -333,8 +355,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             t0 = clock()
             fr.hash_ok = all(f.result() == d.hash[c] for c, f in enumerate(futs))
             st.add("hash_wait", clock() - t0)
-            if verify_hash and not fr.hash_ok:
-                raise HashMismatch("picture %d (POC %d): decoded picture hash SEI mismatch" % (fr.decode_index, fr.poc))
+        if verify_hash and fr.hash_ok is False:
+            raise HashMismatch("picture %d (POC %d): decoded picture hash SEI mismatch" % (fr.decode_index, fr.poc))
         fr.output_rank = rank
         rank += 1
         return fr

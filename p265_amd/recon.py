@@ -183,6 +183,21 @@ def export_coefficients(spec, bit_depth):
     return [int(v) for v in out]
 
 
+def plane_hash_host(plane, hash_type, seg_words=0):
+    """decoded_picture_hash value (D.3.19) of one uint8 or uint16 plane (any row stride), as the SEI carries it,
+    through p265r_plane_hash_host: the split arithmetic of the device kernels on the host, the message cut into
+    segments of ``seg_words`` 32-bit words (0: one) that are combined last first.  Host only: no context."""
+    p = np.asarray(plane)
+    if p.ndim != 2 or p.dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)) or p.strides[1] != p.itemsize:
+        raise ValueError("plane: a 2-D uint8 or uint16 array with contiguous rows")
+    if int(hash_type) not in _lib.HASH_BYTES:
+        raise _lib.P265RError(_lib.EINVAL, "p265r_plane_hash_host")
+    out = (ctypes.c_uint8 * 16)()
+    _lib.check(_lib.load().p265r_plane_hash_host(p.ctypes.data, p.shape[1], p.shape[0], p.strides[0], p.itemsize,
+                                                 int(hash_type), int(seg_words), out), "p265r_plane_hash_host")
+    return bytes(out)[:_lib.HASH_BYTES[int(hash_type)]]
+
+
 class DevicePlane:
     """One plane of one exported frame in device memory: a version-3 ``__cuda_array_interface__`` that array
     libraries on the same GPU wrap without a copy.  The memory belongs to the DeviceFrames it came from."""
@@ -496,6 +511,31 @@ class ReconContext:
         _lib.check(self.lib.p265r_batch_job_count(self.handle, batch.handle, ctypes.byref(lu), ctypes.byref(ch)),
                    "p265r_batch_job_count")
         return int(lu.value), int(ch.value)
+
+    # ---- device-side picture hash ------------------------------------------------------
+    def hash_async(self, batch, hash_type):
+        """Enqueue, behind every run and export of the batch so far, the decoded picture hash (D.3.19;
+        _lib.HASH_MD5 / HASH_CRC / HASH_CHECKSUM) of its output planes on the device and return at once
+        (p265r_batch_hash_async)."""
+        _lib.check(self.lib.p265r_batch_hash_async(self.handle, batch.handle, int(hash_type)), "p265r_batch_hash_async")
+
+    def hash_read(self, batch):
+        """Wait for the batch's lane; -> uint8 array [n_pictures, 3, 16] of the last hash_async, each plane's
+        16 bytes in the SEI's form (p265r_batch_hash_read: 48 bytes per picture).  Raises like status()."""
+        n = len(batch.pics)
+        out = np.zeros((n, 3, 16), np.uint8)
+        _lib.check(self.lib.p265r_batch_hash_read(self.handle, batch.handle,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), 48 * n),
+                   "p265r_batch_hash_read")
+        return out
+
+    def picture_hash(self, batch, hash_type):
+        """hash_async + hash_read: per picture three ``bytes`` (Y, Cb, Cr) of the SEI's length (16, 2 or 4)."""
+        if int(hash_type) not in _lib.HASH_BYTES:
+            raise _lib.P265RError(_lib.EINVAL, "p265r_batch_hash_async")
+        self.hash_async(batch, hash_type)
+        nb = _lib.HASH_BYTES[int(hash_type)]
+        return [[h[c, :nb].tobytes() for c in range(3)] for h in self.hash_read(batch)]
 
     # ---- device-side output -----------------------------------------------------------
     def export_layout(self, spec, pic=None):
