@@ -12,17 +12,12 @@
 // 32x32, striding the TB's entries) and streams the tile out with 16 B per lane, coalesced: the pool is
 // written exactly once, with no memset of the slabs and no 2-byte global stores.  The transform-skip
 // slab mixes TB sizes: a wave per TB there, placed by its job record.
-// A/B (-DP265R_EXPAND_SCATTER=1): hipMemsetAsync of the slabs + one 16-bit global store per entry.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "residual.h"
 
 namespace p265r {
-
-#ifndef P265R_EXPAND_SCATTER
-#define P265R_EXPAND_SCATTER 0
-#endif
 
 constexpr int kExpandTile = 1024;        // int16 per wave tile
 constexpr int kExpandWaves = 4;          // waves per block
@@ -84,23 +79,6 @@ __global__ __launch_bounds__(64 * kExpandWaves) void coef_expand_jobs_kernel(int
     __syncthreads();
     uint4* dst = reinterpret_cast<uint4*>(pool + job.off);
     for (int k = lane; k * 8 < nn; k += 64) dst[k] = reinterpret_cast<const uint4*>(tile)[k];
-}
-
-// A/B baseline: the slabs zeroed by a memset, LPT lanes per job, one 16-bit global store per entry.
-template <int LPT>
-__global__ __launch_bounds__(256) void coef_scatter_kernel(int16_t* __restrict__ pool, const ResJob* __restrict__ jobs,
-                                                          const uint32_t* __restrict__ begin,
-                                                          const uint32_t* __restrict__ ent, int n_jobs) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long j = gid / LPT;
-    if (j >= n_jobs) return;
-    const ResJob job = jobs[j];
-    const uint32_t nn = 1u << (2 * min(max((int)job.log2, 2), 5));
-    const uint32_t e1 = begin[j + 1];
-    for (uint32_t e = begin[j] + (uint32_t)(gid % LPT); e < e1; e += LPT) {
-        const uint32_t v = ent[e];
-        pool[job.off + (v & (nn - 1))] = (int16_t)(v >> 16);
-    }
 }
 
 }  // namespace p265r

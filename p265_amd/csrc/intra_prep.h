@@ -218,13 +218,12 @@ __device__ __forceinline__ uint32_t job_w1(uint32_t w0, uint32_t w5, uint32_t an
 __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict__ pics, Geo g, BatchView v) {
     __shared__ LumaJobLds sj[kMaxCtuLuma];
     __shared__ ChromaJobLds sc[kMaxCtuChroma];
-    P265R_BW_PRIO_SET();
     const DevPic P = pics[blockIdx.z];
     // CTU records from the batch layout (no wait for the DevPic load: both in flight together;
     // slots of the context size, a ragged batch's smaller pictures use the front of theirs)
     const p265r_ctu* ctus = v.ctus0 + (size_t)blockIdx.z * g.wc * g.hc;
     const int cx = blockIdx.x, cy = blockIdx.y;
-    if (P265R_RAGGED && g.ragged) {
+    if (g.ragged) {
         g = pic_geo(g, (uint32_t)__builtin_amdgcn_readfirstlane((int)P.wh));
         if (cx >= g.wc || cy >= g.hc) return;
     }
@@ -355,10 +354,7 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
                                 coded(fh0) << 28 | coded(fh1) << 29 | (m_full ? J_ALL : 0u) | (m_none ? J_NONE : 0u);
             const uint32_t w2 = mlo;
             // fast path: one contiguous run of available units [ulo, uhi] -> sample bounds [fa, la]
-#ifndef P265R_FAST16
-#define P265R_FAST16 1
-#endif
-            const bool fast_size = ((c == 0) & (n <= (P265R_FAST16 ? 16 : 8))) | ((cm == 3u) & (n <= (g.quad & 4 ? 4 : 8)));
+            const bool fast_size = ((c == 0) & (n <= 16)) | ((cm == 3u) & (n <= (g.quad & 4 ? 4 : 8)));
             const int US = c ? 1 : 2;
             const int ulo = mlo ? __ffs((int)mlo) - 1 : 32;
             const int uhi = mhi ? 32 : 31 - __clz((int)(mlo | 1u));
@@ -489,11 +485,7 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
         typedef unsigned int u4 __attribute__((ext_vector_type(4)));
         *(__attribute__((address_space(1))) u4*)(P.jcount + 4 * addr) =
             u4{(uint32_t)n_out | (uint32_t)c_out << 16,
-#ifdef P265R_TR_BROKEN      // negative test of the row kernel's top-right self-check: no job waits
-               (uint32_t)n_out | (uint32_t)c_out << 16,
-#else
                (uint32_t)(tr_l < 0 ? n_out : tr_l) | (uint32_t)(tr_c < 0 ? c_out : tr_c) << 16,
-#endif
                (uint32_t)br_l | (uint32_t)br_c << 16, 0u};
     }
 }

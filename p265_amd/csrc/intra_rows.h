@@ -30,21 +30,12 @@
 
 namespace p265r {
 
-// s_sleep argument between two polls of a row-kernel dependency wait
-#ifndef P265R_SPIN_SLEEP
-#define P265R_SPIN_SLEEP 8
-#endif
-
-// SGPR bases of the job loop (LDS base, angle tables, Cb line) behind opaque s_mov copies per job (1, A/B),
-// or left to the compiler (0: round 5, with 24-B job records, 5.26-5.27 vs 5.30 ms per pipelined step)
-#ifndef P265R_OPAQUE_S
-#define P265R_OPAQUE_S 0
-#endif
-
-// intraPredAngle 0 (modes 10 / 26) as plain copies in the fast paths (0 = the generic angular code)
-#ifndef P265R_HV_FAST
-#define P265R_HV_FAST 1
-#endif
+// s_sleep argument between two polls of a row-kernel dependency wait, and of the cross-group kernel's
+// progress polls
+constexpr int kSpinSleep = 8;
+constexpr int kXgSleep = 8;
+// every 2^kRowPrioShift CTU rows one wave priority step (intra_rows_kernel, at a row's start)
+constexpr int kRowPrioShift = 3;
 
 #ifdef P265R_ISA_MARK                    // tools/isa.sh: comment markers in the device assembly
 #define P265R_MARK(x) asm volatile("; MARK " x)
@@ -170,13 +161,10 @@ __device__ __forceinline__ int ang_inv(uint32_t angw) {
 // the two samples 8.4.4.2.6 interpolates (ds_bpermute byte addresses), byte 2 = iFact, byte 3 =
 // 32 - iFact.  Quad stages read their sample's entry with the stage's gather, so an angular stage
 // costs two bpermutes and the weighting instead of the projection arithmetic.
-// AngTab8 (P265R_ANGTAB8): the same for 8x8 blocks (35 x 64 dwords), read by the fast luma 8x8
+// AngTab8: the same for 8x8 blocks (35 x 64 dwords), read by the fast luma 8x8
 // and Cb+Cr 8x8 jobs.
-#ifndef P265R_ANGTAB8
-#define P265R_ANGTAB8 1
-#endif
 constexpr int kAngTab4Bytes = 35 * 16 * 4;
-constexpr int kAngTab8Bytes = P265R_ANGTAB8 ? 35 * 64 * 4 : 0;
+constexpr int kAngTab8Bytes = 35 * 64 * 4;
 constexpr int kAngTabBytes = kAngTab4Bytes + kAngTab8Bytes;
 template <int LOG2>
 __device__ __forceinline__ uint32_t angtab_entry(int m, int p) {
@@ -214,31 +202,6 @@ struct WaveLdsT {                // one wave's private CTU state (4564 B at 8 bi
     };
 };
 using WaveLds = WaveLdsT<uint8_t>;
-// timing experiment (wrong output): every residual load of the row kernel inside one 8-KB window
-#ifdef P265R_RES_FAKE
-#define P265R_RI(x) ((x) & 4095)
-#else
-#define P265R_RI(x) (x)
-#endif
-#ifndef P265R_XG_SLEEP
-#define P265R_XG_SLEEP 8                 // s_sleep between the cross-group kernel's progress polls (A/B knob)
-#endif
-#ifndef P265R_XG_PRE
-#define P265R_XG_PRE 0                   // XG: the next CTU's first residual fetched at the publish (A/B knob)
-#endif
-#ifndef P265R_PIPE_PRIO
-#define P265R_PIPE_PRIO 0                // A/B: s_setprio of the pipelined (W = 8) row kernel's waves
-#endif
-#ifndef P265R_LATE_REC
-#define P265R_LATE_REC 0                 // 1: the next job's record read after the job (A/B: slower)
-#endif
-#ifndef P265R_QUAD_COMPOSED
-#define P265R_QUAD_COMPOSED 0            // A/B: composed quad-stage references in the cross-group kernel (quad_stage_c):
-                                         // parity green, C5 intra 2.11-2.14 -> 2.31-2.34 ms (3 reps): not kept
-#endif
-#ifndef P265R_TR_DEFER
-#define P265R_TR_DEFER 1                 // 0: wait for the top-right CTU before the CTU starts (A/B knob)
-#endif
 // job word w0 addresses a TB origin as yr * 64 + xr (luma) or 4096 + yr * 32 + xr (chroma,
 // intra_prep.h); WaveLds sample of that origin = w0 offset + kOrg[chroma] (sample units: bytes at 8 bits)
 template <typename T> constexpr uint32_t kOrgLT = (uint32_t)(offsetof(WaveLdsT<T>, y) / sizeof(T));
@@ -524,7 +487,7 @@ __device__ __forceinline__ int fast_pred(int mode, uint32_t angw, int v, int x, 
     int pred;
     // angular modes first (the most frequent path tests one condition: modes 2..34)
     if (mode >= 2) {
-        if (P265R_HV_FAST && (TAB ? (mode & ~16) == 10 : (angw & 0xffu) == 0u)) {
+        if (TAB ? (mode & ~16) == 10 : (angw & 0xffu) == 0u) {
             // modes 10 / 26 (intraPredAngle 0): a copy of the column left / the row above, plus the
             // luma boundary smoothing of 8.4.4.2.6 (fast jobs are n < 32) - no projection arithmetic
             const bool vert = mode >= 18;
@@ -547,15 +510,9 @@ __device__ __forceinline__ int fast_pred(int mode, uint32_t angw, int v, int x, 
             const int pa = __mul24(along + 1, ang);
             const int idx = pa >> 5, fact = pa & 31;
             const int nr0 = -1 - across - idx;                       // -(iIdx + across + 1)
-            const bool bflt = !P265R_HV_FAST && !PAIR && (mode == 26 || mode == 10);   // HV_FAST: copies above
-            const int k1 = ang_ref<2 * n>(nr0 - 1, ia, ns);          // computed unconditionally: a select, no branch
-            const int i1 = bflt ? (vert ? 2 * n - 1 - y : 2 * n + 1 + x) : k1;
-            const int a = ref(ang_ref<2 * n>(nr0, ia, ns)), b = ref(i1);
+            const int k1 = ang_ref<2 * n>(nr0 - 1, ia, ns);          // (b's index first: the instruction order of the tuned build)
+            const int a = ref(ang_ref<2 * n>(nr0, ia, ns)), b = ref(k1);
             pred = (__mul24(32 - fact, a) + __mul24(fact, b) + 16) >> 5;   // = a when iFact = 0 (b then unused)
-            if (bflt) {                                              // modes 26 / 10, luma: boundary smoothing
-                const int edge = clip_pel(uref(vert ? 2 * n + 1 : 2 * n - 1) + ((b - uref(2 * n)) >> 1), maxv);
-                pred = (vert ? x : y) == 0 ? edge : pred;
-            }
         }
     } else if (mode == 0) {
         const int lft = ref(2 * n - 1 - y), top = ref(2 * n + 1 + x);
@@ -615,7 +572,7 @@ __device__ __forceinline__ void recon_fast(uint32_t lbase, uint32_t line_top, ui
     const uint32_t sa = tb + sref + (sref < th ? (lb - tb) - (uint32_t)(sref * (ls + 1)) : 0u);
     const int raw = (int)*ldsT<T>(sa);
     // luma: this sample's angular table entry (AngTab4 / AngTab8), read together with the gather
-    constexpr bool TAB = !PAIR && (LOG2 == 2 || (LOG2 == 3 && P265R_ANGTAB8));
+    constexpr bool TAB = !PAIR && (LOG2 == 2 || LOG2 == 3);
     uint32_t te = w1;
     if constexpr (TAB) {
         const uint32_t t0 = tab + (LOG2 == 3 ? (uint32_t)kAngTab4Bytes : 0u);
@@ -702,7 +659,7 @@ __device__ __forceinline__ void recon_fast16(uint32_t lbase, uint32_t line_top, 
             const int sl = x == 0 ? lft : dc, st = y == 0 ? top : dc;
             pred[i] = (x == 0 || y == 0) ? (sl + st + 2 * dc + 2) >> 2 : dc;
         }
-    } else if (P265R_HV_FAST && (w1 & 0xffu) == 0u) {        // modes 10 / 26: copies + boundary smoothing
+    } else if ((w1 & 0xffu) == 0u) {                         // modes 10 / 26: copies + boundary smoothing
         if (mode >= 18) {
             const int e = clip_pel(uref(2 * n + 1) + ((ref(2 * n - 1 - y) - uref(2 * n)) >> 1), maxv);
 #pragma unroll
@@ -728,23 +685,15 @@ __device__ __forceinline__ void recon_fast16(uint32_t lbase, uint32_t line_top, 
             for (int m = 0; m < 5; ++m) q[m] = ref(refk(x0 + idx + 1 + m, true));
 #pragma unroll
             for (int i = 0; i < 4; ++i) pred[i] = (__mul24(32 - fact, q[i]) + __mul24(fact, q[i + 1]) + 16) >> 5;
-            if (!P265R_HV_FAST && mode == 26) {               // x == 0: boundary smoothing (HV_FAST: above)
-                const int e = clip_pel(uref(2 * n + 1) + ((ref(2 * n - 1 - y) - uref(2 * n)) >> 1), maxv);
-                pred[0] = x0 == 0 ? e : pred[0];
-            }
         } else {                                              // horizontal: projection column per sample
-            const int corner = uref(2 * n), left0 = uref(2 * n - 1);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int x = x0 + i;
                 const int pa = __mul24(x + 1, ang);
                 const int idx = pa >> 5, fact = pa & 31;
                 const int r0 = y + idx + 1;
-                const int a = ref(refk(r0, false));
-                const int k1 = refk(r0 + 1, false);
-                const int b = ref((!P265R_HV_FAST && mode == 10) ? 2 * n + 1 + x : k1);
+                const int a = ref(refk(r0, false)), b = ref(refk(r0 + 1, false));
                 pred[i] = (__mul24(32 - fact, a) + __mul24(fact, b) + 16) >> 5;
-                if (!P265R_HV_FAST && mode == 10) pred[i] = y == 0 ? clip_pel(left0 + ((b - corner) >> 1), maxv) : pred[i];
             }
         }
     }
@@ -780,7 +729,7 @@ __device__ __forceinline__ uint32_t cpred(int mode, uint32_t angw, uint32_t v, i
             const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((angw >> 8) & 0xffu), (int)v);
             return pang<T>(angw >> 24, a, (angw >> 16) & 0xffu, b);
         }
-        if (P265R_HV_FAST && (angw & 0xffu) == 0u)              // modes 10 / 26: a copy (no chroma smoothing)
+        if ((angw & 0xffu) == 0u)                               // modes 10 / 26: a copy (no chroma smoothing)
             return ref(mode >= 18 ? 2 * n + 1 + x : 2 * n - 1 - y);
         const int ang = (int)(int8_t)(angw & 0xffu);
         const int ia = ang_inv(angw);
@@ -839,14 +788,11 @@ __device__ __forceinline__ void recon_cfast8(uint32_t lbase, uint32_t line_cb, u
     const uint32_t sa = tb + sref + (left ? (lb - tb) - (uint32_t)(sref * (ls + 1)) : 0u);
     const uint32_t dcr = left ? (xr == 0 ? 32u : 1024u) : (yr == 0 ? cw : 1024u);
     const uint32_t cb = *ldsT<T>(sa), cr = *ldsT<T>(sa + dcr);
-    uint32_t te = w1;
-    if constexpr (P265R_ANGTAB8) {                            // AngTab8 entry of sample lane
-        te = *lds32(tab + (uint32_t)kAngTab4Bytes + (uint32_t)mode * 256u + (uint32_t)lane * 4u);
-        asm volatile("" : "+v"(te));
-    }
+    uint32_t te = *lds32(tab + (uint32_t)kAngTab4Bytes + (uint32_t)mode * 256u + (uint32_t)lane * 4u);   // AngTab8 entry of sample lane
+    asm volatile("" : "+v"(te));
     const uint32_t v = (w0 & J_NONE) ? (uint32_t)((maxv + 1) >> 1) * 0x00010001u : (cb | cr << 16);
     const int x = lane & 7, y = lane >> 3;
-    const uint32_t rec = cquad_recon(cpred<3, (bool)P265R_ANGTAB8, T>(mode, te, v, x, y, k), (uint32_t)r32, maxv);
+    const uint32_t rec = cquad_recon(cpred<3, true, T>(mode, te, v, x, y, k), (uint32_t)r32, maxv);
     const uint32_t da = orgA + (uint32_t)(y * ist + x);
     *ldsT<T>(da) = (T)(rec & 0xffffu);
     *ldsT<T>(da + 1024) = (T)(rec >> 16);
@@ -889,114 +835,6 @@ __device__ __forceinline__ int quad_stage(int rec, int ext, int lane, int mode, 
     }
 }
 
-// One quad stage with COMPOSED reference reads (the latency layouts, P265R_QUAD_COMPOSED): every reference
-// the stage's prediction reads is taken straight from its source register -- Clip3(fa, la, i) mapped by the
-// stage's affine map onto the external samples or the stages already reconstructed -- instead of first
-// gathering the stage's reference vector and then reading it: one ds_bpermute round trip per stage instead
-// of two, for a few more VALU (the index map per read) and the stage's AngTab4 entry read ahead with the
-// external gather.  Luma stages with two sources read one packed register (rec | ext << 16); chroma values
-// are Cb | Cr pairs already, so a chroma read takes both candidates and selects.  Same arithmetic as
-// quad_stage (fast_pred<2, false, true> / cpred<2, true>), bit for bit.
-template <int Q, bool CH, typename T = uint8_t>
-__device__ __forceinline__ int quad_stage_c(int rec, int ext, int lane, int mode, bool none, int fa, int la,
-                                            uint32_t te, int r16, int qid, int x, int y, int maxv = 255) {
-    constexpr int n = 4;
-    const int half_v = (maxv + 1) >> 1;
-    const uint32_t none_v = CH ? (uint32_t)half_v * 0x00010001u : (uint32_t)half_v;
-    // source of substituted reference s: (lane of the source register, from ext?)
-    auto src_lane = [](int s) -> int {
-        if constexpr (Q == 0) return s <= 8 ? 8 - s : s + 4;
-        else if constexpr (Q == 1) return s < 8 ? 59 - 8 * s : s + 8;
-        else if constexpr (Q == 2) return s <= 8 ? 12 - s : s + 15;
-        else return s <= 8 ? 91 - 8 * s : s + 19;
-    };
-    auto from_ext = [](int s) -> bool {
-        if constexpr (Q == 0) return true;
-        else if constexpr (Q == 1) return s >= 8;
-        else if constexpr (Q == 2) return s <= 8;
-        else return false;
-    };
-    // luma, two sources: one packed register, the half picked after the read
-    const int P = (Q == 1 || Q == 2) && !CH ? (int)(((uint32_t)rec & 0xffffu) | (uint32_t)ext << 16) : (Q == 0 ? ext : rec);
-    auto cref = [&](int i) -> uint32_t {                           // per-lane reference index i
-        const int s = min(max(i, fa), la);
-        const int sl = src_lane(s) << 2;
-        uint32_t v;
-        if constexpr (Q == 0 || Q == 3) {
-            v = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, P);
-        } else if constexpr (!CH) {
-            const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, P);
-            v = from_ext(s) ? w >> 16 : w & 0xffffu;
-        } else {
-            const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, rec), b = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, ext);
-            v = from_ext(s) ? b : a;
-        }
-        if constexpr (Q == 0) v = none ? none_v : v;
-        return v;
-    };
-    auto uref = [&](int i) -> uint32_t {                           // wave-uniform reference index i
-        const int s = __builtin_amdgcn_readfirstlane(min(max(i, fa), la));
-        const int sl = src_lane(s);
-        uint32_t v;
-        if constexpr (Q == 0 || Q == 3) {
-            v = (uint32_t)__builtin_amdgcn_readlane(P, sl);
-        } else if constexpr (!CH) {
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane(P, sl);
-            v = from_ext(s) ? w >> 16 : w & 0xffffu;
-        } else {
-            v = from_ext(s) ? (uint32_t)__builtin_amdgcn_readlane(ext, sl) : (uint32_t)__builtin_amdgcn_readlane(rec, sl);
-        }
-        if constexpr (Q == 0) v = none ? none_v : v;
-        return v;
-    };
-    const bool in = (lane >= n && lane < 2 * n) || (lane > 2 * n && lane <= 3 * n);   // DC sum lanes
-    if constexpr (CH) {
-        constexpr uint32_t rnd = (uint32_t)n * 0x00010001u, msk = (0xffffu >> 3) * 0x00010001u;
-        uint32_t pred;
-        if (mode >= 2) {                                           // AngTab4 entry (modes 10 / 26 included: fact 0)
-            const uint32_t a = cref((int)((te & 0xffu) >> 2)), b = cref((int)(((te >> 8) & 0xffu) >> 2));
-            pred = ((pmul<T>(te >> 24, a) + pmul<T>((te >> 16) & 0xffu, b) + 0x00100010u) >> 5) & 0x07ff07ffu;
-        } else if (mode == 0) {
-            const uint32_t lft = cref(2 * n - 1 - y), top = cref(2 * n + 1 + x);
-            const uint32_t sum = pmul<T>(n - 1 - x, lft) + pmul<T>(x + 1, uref(3 * n + 1)) + pmul<T>(n - 1 - y, top) +
-                                 pmul<T>(y + 1, uref(n - 1)) + rnd;
-            pred = (sum >> 3) & msk;
-        } else {
-            const uint32_t vk = cref(lane);
-            const uint32_t sum = (uint32_t)wave_sum<false, 1>(in ? (int)vk : 0, 0) + rnd;
-            pred = (sum >> 3) & msk;
-        }
-        const int rq = (int)cquad_recon(pred, (uint32_t)r16, maxv);
-        return qid == Q ? rq : rec;
-    } else {
-        int pred;
-        if (mode >= 2) {
-            if (P265R_HV_FAST && (mode & ~16) == 10) {             // modes 10 / 26: copies + boundary smoothing
-                const bool vert = mode >= 18;
-                pred = (int)cref(vert ? 2 * n + 1 + x : 2 * n - 1 - y);
-                const int b = (int)cref(vert ? 2 * n - 1 - y : 2 * n + 1 + x);
-                const int edge = clip_pel((int)uref(vert ? 2 * n + 1 : 2 * n - 1) + ((b - (int)uref(2 * n)) >> 1), maxv);
-                pred = (vert ? x : y) == 0 ? edge : pred;
-            } else {
-                const int a = (int)cref((int)((te & 0xffu) >> 2)), b = (int)cref((int)(((te >> 8) & 0xffu) >> 2));
-                pred = (__mul24((int)(te >> 24), a) + __mul24((int)((te >> 16) & 0xffu), b) + 16) >> 5;
-            }
-        } else if (mode == 0) {
-            const int lft = (int)cref(2 * n - 1 - y), top = (int)cref(2 * n + 1 + x);
-            pred = (__mul24(n - 1 - x, lft) + __mul24(x + 1, (int)uref(3 * n + 1)) + __mul24(n - 1 - y, top) +
-                    __mul24(y + 1, (int)uref(n - 1)) + n) >> 3;
-        } else {
-            const int vk = (int)cref(lane);
-            const int lft = (int)cref(2 * n - 1 - y), top = (int)cref(2 * n + 1 + x);
-            const int dc = (wave_sum<false, 1>(in ? vk : 0, 0) + n) >> 3;
-            const int sl = x == 0 ? lft : dc, st = y == 0 ? top : dc;
-            pred = (x == 0 || y == 0) ? (sl + st + 2 * dc + 2) >> 2 : dc;
-        }
-        const int rq = clip_pel(pred + r16, maxv);
-        return qid == Q ? rq : rec;
-    }
-}
-
 // 4x4 QUAD job (J5_QUAD, intra_prep.h): the four fast 4x4 TBs of one 8x8 luma region (CH =
 // false), or the four Cb+Cr 4x4 pairs of one 8x8 chroma region (CH = true), in one job.  Lane
 // l = region sample (l & 7, l >> 3); the 25 external reference samples (column x = -1, rows
@@ -1005,7 +843,7 @@ __device__ __forceinline__ int quad_stage_c(int rec, int ext, int lane, int mode
 // buffer, and pack them), the four stages pass their samples to each other through registers
 // (ds_bpermute), and the region is written to LDS once.  r16 = this lane's residual sample
 // (chroma: the packed Cb | Cr << 16 pair); line_top = the row above the CTU (chroma: the Cb line).
-template <bool CH, typename T = uint8_t, bool COMP = false>
+template <bool CH, typename T = uint8_t>
 __device__ __forceinline__ void recon_quad(uint32_t lbase, uint32_t line_top, uint32_t cw, uint32_t w0, uint32_t w1,
                                            uint32_t w2, uint32_t tab, int r16, int lane, int maxv = 255) {
     constexpr int ist = CH ? 32 : 64, last = ist - 1;           // interior stride, last row / column
@@ -1035,19 +873,6 @@ __device__ __forceinline__ void recon_quad(uint32_t lbase, uint32_t line_top, ui
     // (pinned at the stage start: the read then shares the gather's LDS wait instead of adding one)
     auto ang = [&](uint32_t m) { uint32_t te = *lds32(tab + m * 64u + pos4); asm volatile("" : "+v"(te)); return te; };
     int rec = 0;
-    if constexpr (COMP) {
-        // composed stages: the four AngTab4 entries read with the external gather (one LDS round trip)
-        const uint32_t m0 = (w0 >> 17) & 63u, m1 = (w0 >> 23) & 63u, m2 = w1 & 63u, m3 = (w1 >> 6) & 63u;
-        const uint32_t t0 = ang(m0), t1 = ang(m1), t2 = ang(m2), t3 = ang(m3);
-        rec = quad_stage_c<0, CH, T>(rec, ext, lane, (int)m0, (w0 >> 29) & 1u, (int)((w1 >> 14) & 31u), (int)((w1 >> 19) & 31u),
-                                     t0, r16, qid, xs, ys, maxv);
-        rec = quad_stage_c<1, CH, T>(rec, ext, lane, (int)m1, false, (int)((w1 >> 24) & 31u), (int)(w2 & 31u),
-                                     t1, r16, qid, xs, ys, maxv);
-        rec = quad_stage_c<2, CH, T>(rec, ext, lane, (int)m2, false, (int)((w2 >> 5) & 31u), (int)((w2 >> 10) & 31u),
-                                     t2, r16, qid, xs, ys, maxv);
-        rec = quad_stage_c<3, CH, T>(rec, ext, lane, (int)m3, false, (int)((w2 >> 15) & 31u), (int)((w2 >> 20) & 31u),
-                                     t3, r16, qid, xs, ys, maxv);
-    } else {
     P265R_MARK("quad_stage0");
     {
         const uint32_t m = (w0 >> 17) & 63u;
@@ -1072,7 +897,6 @@ __device__ __forceinline__ void recon_quad(uint32_t lbase, uint32_t line_top, ui
         rec = quad_stage<3, CH, T>(rec, ext, lane, (int)m, (w1 >> 13) & 1u, (int)((w2 >> 15) & 31u), (int)((w2 >> 20) & 31u),
                                    ang(m), r16, qid, xs, ys, maxv);
     }
-    }
     P265R_MARK("quad_store");
     const uint32_t da = lbase + (CH ? kOrgCT<T> : kOrgLT<T>) + (uint32_t)ofs + (uint32_t)((lane >> 3) * ist + (lane & 7));
     *ldsT<T>(da) = (T)((uint32_t)rec & 0xffffu);
@@ -1080,11 +904,10 @@ __device__ __forceinline__ void recon_quad(uint32_t lbase, uint32_t line_top, ui
     wave_sync();
 }
 
-// WPE = waves per SIMD the register allocation must allow (1: unconstrained).  W = 10 / 12 need
-// 5 / 6 for two workgroups per CU (at most 96 / 80 VGPRs).  W = 8 comes twice: unconstrained
-// (≈100 VGPRs) for a batch that runs alone, and register-lean (WPE 6: 80 VGPRs, a few spills)
-// for batches overlapping other batches' residual / loop-filter kernels, whose waves then
-// fit beside it on every SIMD (p265r.hip launch_rows; measured in DESIGN.md §6).
+// WPE = waves per SIMD the register allocation must allow (1: unconstrained).  W = 12 needs
+// 6 for two workgroups per CU (at most 80 VGPRs).  W = 8 is built register-lean too (WPE 6: 80 VGPRs,
+// a few spills): it runs for batches overlapping other batches' residual / loop-filter kernels, whose
+// waves then fit beside it on every SIMD (p265r.hip launch_rows; measured in DESIGN.md §6).
 //
 // XG (cross-group chains, the latency regime): every picture's luma chain and chroma chain each run on
 // `xg` workgroups of W waves (W = 4: one wave per SIMD, on xg CUs); a wave claims its chain's next row
@@ -1153,13 +976,8 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
 #endif
     for (int i = threadIdx.x; i < fs_count * 2 * g.hc; i += 64 * W) prog[i] = -1;
     for (int i = threadIdx.x; i < 35 * 16; i += 64 * W) atab[i] = angtab_entry<2>(i >> 4, i & 15);
-    if (P265R_ANGTAB8)
-        for (int i = threadIdx.x; i < 35 * 64; i += 64 * W) atab[35 * 16 + i] = angtab_entry<3>(i >> 6, i & 63);
+    for (int i = threadIdx.x; i < 35 * 64; i += 64 * W) atab[35 * 16 + i] = angtab_entry<3>(i >> 6, i & 63);
     __syncthreads();
-#if P265R_PIPE_PRIO > 0
-    // A/B: the pipelined build's waves issue ahead of the other lanes' residual / prep / SAO waves
-    if (W == 8 && !split) __builtin_amdgcn_s_setprio(P265R_PIPE_PRIO);
-#endif
 
     const int G = split ? (int)(gridDim.x >> 1) : (int)gridDim.x;
     const int b = split ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
@@ -1189,7 +1007,7 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
             if (__builtin_amdgcn_readfirstlane(XG ? __hip_atomic_load(gptr(err_flag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                                   : __hip_atomic_load(&ctl.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
                 return false;                               // (XG: any chain's failure ends every wait)
-            __builtin_amdgcn_s_sleep(XG ? P265R_XG_SLEEP : P265R_SPIN_SLEEP);   // 64 cycles per unit; each poll costs issue slots
+            __builtin_amdgcn_s_sleep(XG ? kXgSleep : kSpinSleep);   // 64 cycles per unit; each poll costs issue slots
         }
         __hip_atomic_store(&ctl.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // all lanes, same value
         atomicOr(err_flag, 1);
@@ -1251,7 +1069,7 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
         // this picture's CTU grid and plane size (a ragged batch: DevPic::wh); the row queue, progress
         // words and line buffers keep the context's layout
         int pwc = g.wc, phc = g.hc, pw = g.w, ph = g.h;
-        if (P265R_RAGGED && g.ragged) {
+        if (g.ragged) {
             const Geo pg = pic_geo(g, (uint32_t)__builtin_amdgcn_readfirstlane(*gptr(&Pp->wh)));
             pwc = pg.wc; phc = pg.hc; pw = pg.w; ph = pg.h;
         }
@@ -1290,29 +1108,19 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
             return make_uint4(gload(reinterpret_cast<const uint2*>(ctus + a)).x, jp.x, jp.y, jp.z);
         };
         uint4 hdr_n = hdr_load(cy * pwc);
-#ifndef P265R_ROW_PRIO
-#define P265R_ROW_PRIO 3
-#endif
-#if P265R_ROW_PRIO > 0
         // split mode (small batches, one chain per workgroup): the upper rows of a picture issue
         // first -- they lead the wavefront that every lower row trails (C5: one unit's row kernel
         // 2.595 -> 2.567 ms with 8-row priority bands, 2 reps; 4-row bands 2.60)
         if (split) {
-            const int pr = __builtin_amdgcn_readfirstlane(cy >> P265R_ROW_PRIO);
+            const int pr = __builtin_amdgcn_readfirstlane(cy >> kRowPrioShift);
             if (pr == 0) __builtin_amdgcn_s_setprio(3);
             else if (pr == 1) __builtin_amdgcn_s_setprio(2);
             else if (pr == 2) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
-#endif
         uint4 rec0 = make_uint4(0, 0, 0, 0);
         uint2 rec1 = make_uint2(0, 0);
         bool pre = false;                                  // rec0 / rec1 hold this CTU's first records
-        // XG: the next CTU's first job record and residual, fetched after this CTU's publish (its
-        // residual load then overlaps the next CTU's dependency poll and row-above copy)
-        uint32_t pj0 = 0, pj1 = 0, pj2 = 0, pj3 = 0, pj4 = 0, pj5 = 0;
-        u32x2_t rn_pre = {0u, 0u};
-        bool pre_issued = false;
         for (int cx = 0; cx < pwc; ++cx) {
             // ---- wait for the row above -------------------------------------------------
             // The CTU above (1-CTU lag) before the CTU starts; the top-right CTU (2-CTU lag) before the
@@ -1332,7 +1140,7 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
             const int nt = comp ? n_chroma : (int)(jc & 0xffffu);
             // (deferred only in the latency layouts -- XG and the W = 16 split: the throughput builds keep the
             // 2-CTU-lag start, whose job loop has no per-job test; measured: pipelined step 1.7 % slower with it)
-            constexpr bool kDefer = P265R_TR_DEFER && (XG || W == 16);
+            constexpr bool kDefer = XG || W == 16;
             const int tr = !kDefer ? 0 : comp ? (int)(trw >> 16) : (int)(trw & 0xffffu);   // first job reading the top-right CTU
             const bool tr_ctu = cy > 0 && cx + 1 < pwc;        // a top-right CTU exists (else nothing to wait for)
             // XG progress counts half CTUs (2 per finished CTU, +1 once the left half of the next one's bottom
@@ -1414,13 +1222,13 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 const int ls = 2 * lg - (pr ? 5 : 6);
                 const int S = ls > 0 ? (1 << ls) : 1;
                 const int sidx = hl * S < (1 << (2 * lg)) ? hl * S : 0;
-                return reinterpret_cast<const uint4*>(resid + P265R_RI((int)(h ? w4 : w3)) + (sidx & ~7));
+                return reinterpret_cast<const uint4*>(resid + (int)(h ? w4 : w3) + (sidx & ~7));
             };
             // fast jobs (J5_FAST): one residual sample per lane (2-B load); w3 / w4 already point
             // at the pool, the residual or the zero block, and lanes past the TB read padding
             auto res_fast = [&](uint32_t w0, uint32_t w3, uint32_t w4) {
                 const bool pr = (w0 >> 15) & 3u;
-                return resid + P265R_RI((int)(pr && lane >= 32 ? w4 : w3)) + (pr ? (lane & 31) : lane);
+                return resid + (int)(pr && lane >= 32 ? w4 : w3) + (pr ? (lane & 31) : lane);
             };
             // job records (24 B): 64 at a time into six VGPRs per lane, read per job with v_readlane
             // (scalar loads were measured slower: their lgkmcnt waits serialise with the LDS
@@ -1445,7 +1253,7 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 if (j.w5 & J5_QUAD) {                       // quads: residual = w3 + 16 * code (15: the zero block)
                     const int q = ((lane >> 4) & 2) | ((lane >> 2) & 1);    // sub-TB of sample (x, y) of the 8x8 region
                     const int i = ((lane >> 1) & 12) + (lane & 3);          // sample index in the 4x4 sub-TB
-                    auto at = [&](uint32_t code) { return P265R_RI(code == 15u ? zero_res : (int)j.w3 + (int)(code << 4)) + i; };
+                    auto at = [&](uint32_t code) { return (code == 15u ? zero_res : (int)j.w3 + (int)(code << 4)) + i; };
                     if ((j.w0 >> 15) & 3u) {                                // chroma: Cb | Cr << 16, codes at 8q + 4h
                         const uint32_t codes = j.w4 >> (8 * q);
                         const uint32_t cb = (uint16_t)*gptr(resid + at(codes & 15u));
@@ -1454,11 +1262,11 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                     }
                     return u32x2_t{(uint32_t)(int)*gptr(resid + at((j.w4 >> (4 * q)) & 15u)), 0u};
                 } else if ((j.w5 & J5_FAST) && ((j.w0 >> 13) & 15u) == 13u) { // Cb+Cr 8x8: Cb | Cr << 16 of sample lane
-                    const uint32_t cb = (uint16_t)*gptr(resid + P265R_RI((int)j.w3) + lane);
-                    const uint32_t cr = (uint16_t)*gptr(resid + P265R_RI((int)j.w4) + lane);
+                    const uint32_t cb = (uint16_t)*gptr(resid + (int)j.w3 + lane);
+                    const uint32_t cr = (uint16_t)*gptr(resid + (int)j.w4 + lane);
                     return u32x2_t{cb, cr};     // packed at use: no wait here
                 } else if ((j.w5 & J5_FAST) && ((j.w0 >> 13) & 3u) == 2u) { // 16x16 luma: 4 samples per lane
-                    const u32x2_t d = *reinterpret_cast<const P265R_GLOBAL u32x2_t*>(gptr(resid + P265R_RI((int)j.w3) + 4 * lane));
+                    const u32x2_t d = *reinterpret_cast<const P265R_GLOBAL u32x2_t*>(gptr(resid + (int)j.w3 + 4 * lane));
                     return d;
                 } else if (j.w5 & J5_FAST) {
                     return u32x2_t{(uint32_t)(int)*gptr(res_fast(j.w0, j.w3, j.w4)), 0u};
@@ -1467,17 +1275,11 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
             };
             JobS cur{0, 0, 0, 0, 0, 0};
             if (nt) {
-                if (XG && pre_issued) {
-                    cur = JobS{pj0, pj1, pj2, pj3, pj4, pj5};
-                    rn = rn_pre;
-                } else {
-                    if (!pre) refill(0);
-                    cur = sjob(0);
-                    rn = issue(cur, 0);
-                }
+                if (!pre) refill(0);
+                cur = sjob(0);
+                rn = issue(cur, 0);
             }
             pre = false;
-            pre_issued = false;
             // the top-right wait before job tr (the row above the CTU suffices for the jobs before it)
             const int t_trw = tr_done || tr >= nt ? -1 : tr;
             const int t_half = halfp && br < nt ? br : -1;     // XG: publish the bottom row's left half first
@@ -1492,9 +1294,6 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                         0x3cc3a55au ^ (uint32_t)((cx * 64 + k) * 0x01030507);
                 wave_sync();
             }
-#ifdef P265R_JOB_UNROLL
-#pragma unroll P265R_JOB_UNROLL
-#endif
             for (int t = 0; t < nt; ++t) {
                 P265R_MARK("job_top");
                 if (t == t_trw) {                       // (a failed wait runs on; the loop exits after the job)
@@ -1512,50 +1311,22 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 const int c16 = (int)rn.x, c16m = (int)rn.y;
                 if (t + 1 < nt) {
                     if (((t + 1) & 63) == 0) refill(t + 1);
-#if P265R_LATE_REC
-                    // the next record's residual fields only (its whole record is read after this job, into
-                    // the registers this one held: no per-job copies of the six record words)
-                    const int l = (t + 1) & 63;
-                    auto rl = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane(v, l); };
-                    rn = issue(JobS{rl(rec0.x), 0u, 0u, rl(rec0.w), rl(rec1.x), rl(rec1.y)}, t + 1);
-#else
                     cur = sjob(t + 1);
                     rn = issue(cur, t + 1);
-#endif
                 }
                 const int sel = (int)((w0 >> 13) & 3u) | (((w0 >> 15) & 3u) ? 4 : 0);
                 P265R_MARK("job_dispatch");
-#ifdef P265R_PAD_SALU
-                {   // A/B probe: P265R_PAD_SALU dependent scalar adds per job (issue-bound test)
-                    uint32_t z = w0;
-#pragma unroll
-                    for (int q = 0; q < P265R_PAD_SALU; ++q) asm volatile("s_mov_b32 %0, %0" : "+s"(z));   // (s_mov: leaves SCC alone)
-                    asm volatile("" :: "s"(z));
-                }
-#endif
-#ifdef P265R_PAD_VALU
-                {   // A/B probe: P265R_PAD_VALU dependent vector adds per job
-                    uint32_t z = (uint32_t)lane;
-#pragma unroll
-                    for (int q = 0; q < P265R_PAD_VALU; ++q) asm volatile("v_add_u32 %0, 1, %0" : "+v"(z));
-                    asm volatile("" :: "v"(z));
-                }
-#endif
-                // Opaque copies of the lane id and the LDS bases: keeps the compiler from
+                // Opaque copies of the lane id and the line pointers: keeps the compiler from
                 // hoisting every template's lane-derived constants out of the job loop
-                // (7 inlined instances would otherwise hold them all live: ~150 VGPRs).
+                // (7 inlined instances would otherwise hold them all live: ~150 VGPRs).  The wave-uniform
+                // bases (LDS base, angle tables, Cb line) are left to the compiler (round 5, with 24-B job
+                // records: 5.26-5.27 vs 5.30 ms per pipelined step behind opaque s_mov copies)
                 int ln;
                 asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
                 uint32_t lbase, tl, tc, tcb, tab;
-#if P265R_OPAQUE_S
-                asm volatile("s_mov_b32 %0, %1" : "=s"(lbase) : "s"(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)&L)));
-                asm volatile("s_mov_b32 %0, %1" : "=s"(tab) : "s"(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)atab)));
-                asm volatile("s_mov_b32 %0, %1" : "=s"(tcb) : "s"(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ltop_cb)));
-#else
                 lbase = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)&L);
                 tab = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)atab);
                 tcb = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ltop_cb);
-#endif
                 asm volatile("v_mov_b32 %0, %1" : "=v"(tl) : "v"((uint32_t)(uintptr_t)ltop_l));
                 asm volatile("v_mov_b32 %0, %1" : "=v"(tc) : "v"((uint32_t)(uintptr_t)ltop_c));
                 WaveLdsT<T>& LL = *reinterpret_cast<WaveLdsT<T>*>(lds_ptr(lbase));
@@ -1564,10 +1335,8 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 // (8 bits: the constant 255 folds into every job function, as before the 16-bit path)
                 const int mv = PB == 1 ? 255 : maxv;
                 if (w5 & J5_QUAD) {
-                    // (the latency layout reads the quad stages' references composed: one round trip per stage)
-                    constexpr bool kComp = XG && P265R_QUAD_COMPOSED;
-                    if ((w0 >> 15) & 3u) recon_quad<true, T, kComp>(lbase, tcb, cr_off, w0, w1, w2, tab, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, mv);
-                    else recon_quad<false, T, kComp>(lbase, tl, 0u, w0, w1, w2, tab, c16, ln, mv);
+                    if ((w0 >> 15) & 3u) recon_quad<true, T>(lbase, tcb, cr_off, w0, w1, w2, tab, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, mv);
+                    else recon_quad<false, T>(lbase, tl, 0u, w0, w1, w2, tab, c16, ln, mv);
                 } else if (w5 & J5_FAST) {
                     switch (sel) {
                         case 0: recon_fast<2, false, T>(lbase, tl, w0, w1, w5, c16, ln, tab, mv); break;
@@ -1601,21 +1370,17 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                     }
                 }
 #endif
-#if P265R_LATE_REC
-                if (t + 1 < nt) cur = sjob(t + 1);
-#endif
             }
             if (failed) break;                             // (wait_until published the error)
             // before this CTU's bottom row goes into the line buffer (whether or not a job read it; XG:
             // one line per row, nothing to overwrite)
             if (!XG && !tr_done && !wait_up(cx + 2)) { failed = true; break; }
 
-            int nt2 = 0;
             if (cx + 1 < pwc) {                            // the next CTU's first 64 job records
                 const uint32_t tb2 = (uint32_t)__builtin_amdgcn_readfirstlane(hdr_n.x);
                 const uint32_t jc2 = (uint32_t)__builtin_amdgcn_readfirstlane(hdr_n.y);
                 const int nc2 = (int)(jc2 >> 16);
-                nt2 = comp ? nc2 : (int)(jc2 & 0xffffu);
+                const int nt2 = comp ? nc2 : (int)(jc2 & 0xffffu);
                 const IntraJob* jl2 = jobs + tb2 + (comp ? 0 : nc2);
                 if (lane < nt2) { rec0 = ld16(&jl2[lane].w[0]); rec1 = ld8(&jl2[lane].w[4]); }
                 else { rec0 = make_uint4(0, 0, 0, 0); rec1 = make_uint2(0, 0); }
@@ -1678,12 +1443,6 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 // that announces them; the plane stores are read only by later kernels
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) __hip_atomic_store(xg_prog + cy, tag | (2 * (cx + 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (P265R_XG_PRE && pre && nt2 > 0) {     // (the wait above also covered the record loads)
-                    const JobS c0 = sjob(0);
-                    pj0 = c0.w0; pj1 = c0.w1; pj2 = c0.w2; pj3 = c0.w3; pj4 = c0.w4; pj5 = c0.w5;
-                    rn_pre = issue(c0, 0);
-                    pre_issued = true;
-                }
             } else {
                 __hip_atomic_store(my_prog, tag | (cx + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }

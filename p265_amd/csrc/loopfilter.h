@@ -60,7 +60,7 @@ template <typename M>        // uint8_t: BitDepth 8 (DBK_*); uint16_t: BitDepth 
 __global__ __launch_bounds__(64) void dbk_map_kernel(const DevPic* __restrict__ pics, Geo g) {
     constexpr int EV = sizeof(M) == 1 ? DBK_V : DBK16_V, EH = sizeof(M) == 1 ? DBK_H : DBK16_H;
     const DevPic* P = pics + blockIdx.y;
-    if (P265R_RAGGED && g.ragged) {                                              // grid: the context's CTU count
+    if (g.ragged) {                                              // grid: the context's CTU count
         g = pic_geo(g, (uint32_t)__builtin_amdgcn_readfirstlane((int)P->wh));
         if ((int)blockIdx.x >= g.wc * g.hc) return;
     }
@@ -168,9 +168,7 @@ struct LfCtu {                  // the fields of a neighbouring CTU record the f
     uint8_t  offs;
 };
 
-#ifndef P265R_LF_DBK_THREADS
-#define P265R_LF_DBK_THREADS 192
-#endif
+constexpr int kLfDbkThreads = 192;   // threads of a deblocking workgroup (LfShape::threads)
 
 template <int CTBL> struct LfShape {
     static constexpr int S = 1 << CTBL, SC = S / 2;
@@ -194,7 +192,7 @@ template <int CTBL> struct LfShape {
     // CTB 64, 512 pictures: 64 / 128 / 192 / 256 threads -> 3.62 / 2.83 / 2.64 / 3.42 ms.  SAO
     // alone prefers one unit per thread (256: 1.65 ms, 128: 1.73 ms).  Every phase loops over
     // its tasks, so any multiple of 64 is correct.
-    static constexpr int threads(bool dbk) { return dbk && T1 > P265R_LF_DBK_THREADS ? P265R_LF_DBK_THREADS : T1; }
+    static constexpr int threads(bool dbk) { return dbk && T1 > kLfDbkThreads ? kLfDbkThreads : T1; }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -224,7 +222,7 @@ __device__ __forceinline__ LfWindow lf_window(const DevPic* __restrict__ pics, G
     w.rs = unit - w.pic * n_ctus;
     w.rx = w.rs % gb.wc;
     w.ry = w.rs / gb.wc;
-    if (P265R_RAGGED && gb.ragged) {                              // this picture's size and CTU raster
+    if (gb.ragged) {                              // this picture's size and CTU raster
         g = pic_geo(gb, (uint32_t)__builtin_amdgcn_readfirstlane((int)pics[w.pic].wh));
         w.outside = w.outside || w.rx >= g.wc || w.ry >= g.hc;
         w.rs = w.ry * g.wc + w.rx;

@@ -10,11 +10,11 @@
 
 #include <algorithm>
 #include <array>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -40,34 +40,18 @@
 
 using namespace p265r;
 
-// Experiment knobs (measured-slower or diagnostic variants) are compiled in only with
-// -DP265R_EXPERIMENTS=1 (make variant V=exp FLAGS=-DP265R_EXPERIMENTS=1): P265R_SKIP, P265R_STREAM_PRIO,
-// P265R_PIPE_WAVES, P265R_LEAN=0, P265R_FORK_PREP=2, P265R_ROW_WAVES 4 / 6 / 10 / 16, P265R_DEBUG_SYNC.
-// The product build reads only the knobs the GPU parity matrix sets (tests/test_gpu_parity.py).
-#ifndef P265R_EXPERIMENTS
-#define P265R_EXPERIMENTS 0
-#endif
+// The library reads only the environment knobs the GPU parity matrix sets (tests/test_gpu_parity.py), and
+// P265R_DEBUG_SYNC in -DP265R_DEBUG_DIAG builds.  Retired experiment knobs: EXPERIMENTS.md, "Retired knobs".
+//
 // Stream plan of pipelined contexts (round 5: one interleaved A/B of round 3's head against every round-4
-// step): the round-4 additions below each cost 5-8 % of the pipelined C3 step by adding
+// step): the two round-4 schedules below each cost 5-8 % of the pipelined C3 step by adding
 // streams -- a process's streams map round-robin onto GPU_MAX_HW_QUEUES hardware queues (4), so every
-// extra stream changes which lanes' kernels queue behind which -- and are off (A/B macros only):
+// extra stream changes which lanes' kernels queue behind which -- and are off (the check-variant builds only):
 #ifndef P265R_EARLY_RESIDUAL
 #define P265R_EARLY_RESIDUAL 0     // re-runs: residual + prep start when the batch's previous intra phase ends
 #endif
 #ifndef P265R_PHASE_ORDER
 #define P265R_PHASE_ORDER 0        // pipelined contexts: one intra phase at a time; residual + prep overlap loop filters
-#endif
-#ifndef P265R_SAO_AUX
-#define P265R_SAO_AUX 0            // pipelined chip-filling batches: prep on the lane stream, the loop filters on the
-                                   // lane's aux stream, so the next run's residual + prep overlap this run's SAO
-#endif
-#ifndef P265R_EXPAND_STREAM
-#define P265R_EXPAND_STREAM 0      // sparse upload: 0 the expand kernels follow their chunk's copies on the upload's
-                                   // stream; 1 (A/B) on a second stream gated by an event per chunk, beside the next
-                                   // chunk's copies
-#endif
-#ifndef P265R_SPLIT_W16
-#define P265R_SPLIT_W16 1          // small split batches: W = 16 row kernel (0: the by-run W, A/B)
 #endif
 
 namespace {
@@ -112,39 +96,28 @@ struct p265r_ctx {
     p265r_batch* pending = nullptr;
     std::vector<p265r_picture> pending_pics;
     int schedule = 1;          // 0: one launch per anti-diagonal, 1: CU-local row pipeline
-    int row_waves = 0;         // waves per workgroup of the row pipeline (P265R_ROW_WAVES 8, 12; experiments
-                               // build also 4, 6, 10, 16); 0 = by run: a batch alone 12 (6 per SIMD, 80 VGPRs:
+    int row_waves = 0;         // waves per workgroup of the row pipeline (P265R_ROW_WAVES 8, 12);
+                               // 0 = by run: a batch alone 12 (6 per SIMD, 80 VGPRs:
                                // lowest latency), overlapping other lanes' batches 8 (80 VGPRs: room beside it)
     unsigned lane_busy = 0;    // lanes with a run enqueued since the API last synchronised them (p265r_sync,
                                // p265r_batch_download / p265r_batch_status of a batch on the lane): the row
                                // kernel build of a run follows from the call sequence, not from device timing
     int sao_rows = 1;          // SAO-only batches: 1 16-B strip kernel (CTB 32 / 64; 4-B strip kernel for
                                // CTB 16), 2 4-B strip kernel, 0 loop-filter window kernel (P265R_SAO_ROWS)
-    int skip = 0;              // P265R_SKIP (timing experiments on batch re-runs, p265r_batch_run)
-    int lean = 1;              // experiments: W = 8 row kernel build 0 unconstrained (P265R_LEAN=0), 1 register-lean
-    int split = 1;             // component split of small batches (P265R_SPLIT=0: off; launch_rows_w)
+    int split = 1;            // component split of small batches (P265R_SPLIT=0: off; launch_rows_w)
     int xg = 4;                // workgroups per chain of the cross-group row kernel (P265R_XG; 0: off; launch_rows)
     bool last_split = false;   // the last row-kernel launch was split (p265r_describe)
     bool last_xg = false;      // ... was the cross-group kernel
-    long long row_launches[5] = {0, 0, 0, 0, 0};   // row-kernel launches per build: W = 12, W = 8, W = 16 split,
-                                                   // cross-group, other (experiments) -- p265r_describe
+    long long row_launches[4] = {0, 0, 0, 0};      // row-kernel launches per build: W = 12, W = 8, W = 16 split,
+                                                   // cross-group -- p265r_describe
     int luma_lead = -1;        // rows the luma chain leads the chroma chain in the row queue (P265R_LUMA_LEAD);
                                // -1 = by run: 8 for a batch alone, 5 beside other lanes' batches (round 3,
                                // 2 reps: alone lead 5/7/8/10 -> 4.28/4.23/4.19/4.22 ms, pipelined
                                // 45.5/44.9/44.4/44.7 M CTU/s; round 1, W=8: lead 0/1/2/3/5/8/17 ->
                                // 10.40/10.10/10.40/10.09/10.07/10.35/10.38 ms)
-    bool stream_prio = false;
-    // occupancy caps by dynamic-LDS padding of the SAO / residual launches (P265R_SAO_LDS /
-    // P265R_RES_LDS bytes per block, experiments builds): fewer waves per CU streamed faster in the
-    // HBM probe (tools/bw_probe.hip)
-    int sao_lds = 0, res_lds = 0, prep_lds = 0;
-    int prep_last = 0;             // experiments: P265R_PREP_LAST=1 enqueues the prep kernel after the residual kernels
-    int order_r = 1;               // P265R_ORDER_R=0 (experiments): ordered runs' residual phase waits only for its own batch  // lanes at the highest stream priority, prep streams at the lowest (P265R_STREAM_PRIO)
-    int pipe_waves = 8;        // row pipeline waves per workgroup while other lanes have work (experiments:
-                               // P265R_PIPE_WAVES 4, 6, 8)
     int num_cus = 256;
-    bool debug_sync = false;   // P265R_DEBUG_SYNC=1: synchronise + log after every phase (P265R_DEBUG_DIAG
-                               // builds also trace the row kernel's waves and print placement statistics)
+    bool debug_sync = false;   // P265R_DEBUG_DIAG builds, P265R_DEBUG_SYNC=1: synchronise + log after every phase,
+                               // trace the row kernel's waves and print placement statistics
     // reused across batches: pinned host staging (grow-only) and one freed device allocation
     unsigned char* stage = nullptr;
     size_t stage_bytes = 0;
@@ -177,8 +150,7 @@ struct p265r_ctx {
     // entry begins (grow-only; an upload is complete when it returns, so the next one reuses it)
     void* sp_mem = nullptr;
     size_t sp_bytes = 0;
-    hipStream_t exp_stream = nullptr;       // P265R_EXPAND_STREAM: the expand kernels' stream
-    std::vector<hipEvent_t> exp_ev;         // ... its per-chunk gates (+ one join), and the timed uploads' event pairs
+    std::vector<hipEvent_t> exp_ev;         // timed uploads: an event pair per chunk around its expand kernels
     double last_expand_ms = -1.0;           // expand kernels of the last sparse upload (timing on), p265r_describe
 };
 
@@ -206,8 +178,6 @@ struct p265r_batch {
     std::vector<std::array<int, 2>> size;   // per picture: luma width, height
     uint64_t h2d_bytes = 0;    // host-to-device bytes its upload enqueued (p265r_batch_upload_bytes)
     int runs = 0;              // p265r_batch_run calls so far
-    hipEvent_t sao_done = nullptr;     // P265R_SAO_AUX: recorded on the aux stream after a run's loop filters
-    bool sao_pending = false;          // ... and not yet joined into the lane stream (join_sao)
     std::vector<void*> exp_idx;        // p265r_batch_export: device copies of the pic_index lists of the exports
                                        // enqueued since the lane was last synchronised (p265r_batch_status)
     unsigned long long* d_dig = nullptr;   // p265r_batch_digest_async slots: P265R_DIGEST_SLOTS x n_pics x 3
@@ -219,16 +189,6 @@ struct p265r_batch {
 };
 
 namespace {
-
-// a lane stream: default priority, or the device's highest with P265R_STREAM_PRIO (then the
-// dispatcher prefers the lanes' residual / intra / SAO workgroups over the prep streams')
-hipError_t lane_stream_create(const p265r_ctx* ctx, hipStream_t* st) {
-    if (!ctx->stream_prio) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e != hipSuccess) return e;
-    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest);
-}
 
 #ifdef P265R_DEBUG_DIAG
 // Row-kernel diagnostics (P265R_DEBUG_DIAG builds with P265R_DEBUG_SYNC=1): wave trace of a hung
@@ -279,15 +239,6 @@ void rows_diag(hipStream_t st, const int* dbg, int grid, int W) {
                 life[grid - 1] * 256e-6);
 }
 #endif
-
-// P265R_SAO_AUX: order the batch's lane stream after its last run's loop filters (host-facing reads)
-int join_sao(p265r_batch* b) {
-    if (b->sao_pending) {
-        HIP_TRY(hipStreamWaitEvent(b->stream, b->sao_done, 0));
-        b->sao_pending = false;
-    }
-    return P265R_OK;
-}
 
 // dynamic LDS of the row kernel with W waves and f picture slots (launch_rows_w)
 template <typename T>
@@ -348,7 +299,7 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
     fn<<<grid, 64 * W, lds, st>>>(b->d_pics, b->d_pool, b->d_res, g, b->n_pics, fs, lead, b->d_err, dbg, split ? 1 : 0, xb);
     ctx->last_split = split;
     ctx->last_xg = XG;
-    ++ctx->row_launches[XG ? 3 : (W == 16 ? 2 : (W == 8 ? 1 : (W == 12 ? 0 : 4)))];
+    ++ctx->row_launches[XG ? 3 : (W == 16 ? 2 : (W == 8 ? 1 : 0))];
     HIP_TRY(hipGetLastError());
 #ifdef P265R_DEBUG_DIAG
     if (dbg) {
@@ -362,28 +313,7 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
 // alone: no other lane of the context has a run enqueued (ctx->lane_busy), so this batch's kernels
 // have the GPU to themselves: W = 12 with fair CU sharing; otherwise W = 8 (80 VGPRs, so the residual /
 // prep / SAO waves of the neighbouring batches fit beside it on every SIMD)
-#ifndef P265R_W10_WPE
-#define P265R_W10_WPE 5                  // experiments: the pipelined W = 10 build's waves-per-SIMD attribute
-#endif
 int launch_rows(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
-#if P265R_EXPERIMENTS
-    switch (ctx->row_waves) {
-        case 4: return launch_rows_w<4, 1>(ctx, b, st, alone);
-        case 6: return launch_rows_w<6, 1>(ctx, b, st, alone);
-        case 10: return launch_rows_w<10, 5>(ctx, b, st, alone);
-        case 16: return launch_rows_w<16, 1>(ctx, b, st, alone);
-        default: break;
-    }
-    if (ctx->row_waves == 0 && !alone && ctx->pipe_waves == 4) return launch_rows_w<4, 1>(ctx, b, st, alone);
-    if (ctx->row_waves == 0 && !alone && ctx->pipe_waves == 6) return launch_rows_w<6, 1>(ctx, b, st, alone);
-    if (ctx->row_waves == 0 && !alone && ctx->pipe_waves == 10 && !(ctx->split && 2 * (long long)b->n_pics <= ctx->num_cus))
-        return launch_rows_w<10, P265R_W10_WPE>(ctx, b, st, alone);
-    if (ctx->lean == 0 && (ctx->row_waves == 8 || (ctx->row_waves == 0 && !alone))) return launch_rows_w<8, 1>(ctx, b, st, alone);
-#endif
-    // a batch small enough for the component split with one workgroup per CU (the latency regime:
-    // tile units, the decoder's small batches): W = 16, so every CTU row of a picture's chain can
-    // be in flight at once (a 2-CTU-lag wavefront of 17 rows needs 17 waves; with 12 the rows
-    // after the 12th wait for a whole row to finish)
     // 16-bit samples (BitDepth 9..12): the same row pipeline on 16-bit LDS tiles and line buffers
     // (one workgroup per CU: twice the LDS of a wave); W = 12 alone, W = 8 beside other lanes' work
     if (ctx->geo.pel16) {
@@ -397,11 +327,15 @@ int launch_rows(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
         return w == 12 ? launch_rows_w<12, 1, false, false, uint16_t>(ctx, b, st, alone)
                        : launch_rows_w<8, 1, false, false, uint16_t>(ctx, b, st, alone);
     }
-    // smaller still (every chain on xg CUs of its own): the cross-group kernel, one wave per SIMD
+    // the smallest batches (every chain on xg CUs of its own): the cross-group kernel, one wave per SIMD
     if (ctx->row_waves == 0 && b->d_xg_prog && 2 * (long long)b->n_pics * ctx->xg <= ctx->num_cus)
         return ctx->geo.tr_check ? launch_rows_w<4, 1, true, true>(ctx, b, st, alone)     // (test build of it)
                                  : launch_rows_w<4, 1, true>(ctx, b, st, alone);
-    if (ctx->row_waves == 0 && ctx->split && P265R_SPLIT_W16 && 2 * (long long)b->n_pics <= ctx->num_cus)
+    // a batch small enough for the component split with one workgroup per CU (the latency regime:
+    // tile units, the decoder's small batches): W = 16, so every CTU row of a picture's chain can
+    // be in flight at once (a 2-CTU-lag wavefront of 17 rows needs 17 waves; with 12 the rows
+    // after the 12th wait for a whole row to finish)
+    if (ctx->row_waves == 0 && ctx->split && 2 * (long long)b->n_pics <= ctx->num_cus)
         return launch_rows_w<16, 4>(ctx, b, st, alone);
     const int w = ctx->row_waves ? ctx->row_waves : (alone ? 12 : 8);
     return w == 12 ? launch_rows_w<12, 6>(ctx, b, st, alone) : launch_rows_w<8, 6>(ctx, b, st, alone);
@@ -435,8 +369,8 @@ int launch_loop_filters(p265r_ctx* ctx, p265r_batch* b, const Geo& g, hipStream_
         sao16_strip_kernel<<<blocks, 256, 0, s>>>(b->d_pics, g, b->view, np);
     } else if (sao_only && !g.pel16 && ctx->sao_rows == 1 && g.ctb_log2 >= 5 && g.h % 8 == 0) {
         if (int rc = strip_grid(strip_units(g, strip_samples(16)), np, &blocks)) return rc;
-        if (g.ctb_log2 == 6) sao_strip16_kernel<6><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, np);
-        else sao_strip16_kernel<5><<<blocks, 256, ctx->sao_lds, s>>>(b->d_pics, g, b->view, np);
+        if (g.ctb_log2 == 6) sao_strip16_kernel<6><<<blocks, 256, 0, s>>>(b->d_pics, g, b->view, np);
+        else sao_strip16_kernel<5><<<blocks, 256, 0, s>>>(b->d_pics, g, b->view, np);
     } else if (sao_only && !g.pel16 && ctx->sao_rows) {
         if (int rc = strip_grid(strip_units(g, strip_samples(4)), np, &blocks)) return rc;
         sao_rows_kernel<<<blocks, 256, 0, s>>>(b->d_pics, g, np);
@@ -588,33 +522,16 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     if (const char* v = std::getenv("P265R_ROW_WAVES")) {
         const int w = std::atoi(v);
         if (w == 8 || w == 12) ctx->row_waves = w;
-#if P265R_EXPERIMENTS
-        if (w == 4 || w == 6 || w == 10 || w == 16) ctx->row_waves = w;
-#endif
     }
-#if P265R_EXPERIMENTS
-    for (const char* k : {"P265R_DEBUG_SYNC", "P265R_SKIP", "P265R_LEAN", "P265R_PIPE_WAVES", "P265R_STREAM_PRIO"})
-        if (std::getenv(k)) ctx->describe += std::string(ctx->describe.empty() ? "" : ", ") + "\"" + k + "\"";
-    if (const char* v = std::getenv("P265R_DEBUG_SYNC")) ctx->debug_sync = v[0] == '1';
-    if (const char* v = std::getenv("P265R_SKIP")) ctx->skip = std::atoi(v) & 7;
-    if (const char* v = std::getenv("P265R_LEAN")) ctx->lean = std::atoi(v) == 0 ? 0 : 1;
-    if (const char* v = std::getenv("P265R_FORK_PREP")) ctx->fork_prep = std::min(2, std::max(0, std::atoi(v)));
-    if (const char* v = std::getenv("P265R_PIPE_WAVES")) {
-        const int w = std::atoi(v);
-        if (w == 4 || w == 6 || w == 8 || w == 10) ctx->pipe_waves = w;
+#ifdef P265R_DEBUG_DIAG
+    if (const char* v = std::getenv("P265R_DEBUG_SYNC")) {
+        ctx->debug_sync = v[0] == '1';
+        ctx->describe += std::string(ctx->describe.empty() ? "" : ", ") + "\"P265R_DEBUG_SYNC\"";
     }
-    if (const char* v = std::getenv("P265R_STREAM_PRIO")) ctx->stream_prio = std::atoi(v) != 0;
-    for (const char* k : {"P265R_SAO_LDS", "P265R_RES_LDS", "P265R_PREP_LDS", "P265R_PREP_LAST"})
-        if (std::getenv(k)) ctx->describe += std::string(ctx->describe.empty() ? "" : ", ") + "\"" + k + "\"";
-    if (const char* v = std::getenv("P265R_ORDER_R")) ctx->order_r = std::atoi(v) != 0;
-    if (const char* v = std::getenv("P265R_SAO_LDS")) ctx->sao_lds = std::min(65536, std::max(0, std::atoi(v)));
-    if (const char* v = std::getenv("P265R_RES_LDS")) ctx->res_lds = std::min(32768, std::max(0, std::atoi(v)));
-    if (const char* v = std::getenv("P265R_PREP_LDS")) ctx->prep_lds = std::min(65536, std::max(0, std::atoi(v)));
-    if (const char* v = std::getenv("P265R_PREP_LAST")) ctx->prep_last = std::atoi(v) != 0;
 #endif
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e == hipSuccess) e = lane_stream_create(ctx, &ctx->stream);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e == hipSuccess) ctx->lanes.push_back(ctx->stream);
     if (e == hipSuccess) {
         int8_t ang[35];
@@ -660,7 +577,6 @@ void p265r_destroy(p265r_ctx* ctx) {
     if (ctx->d_sf) (void)hipFree(ctx->d_sf);
     if (ctx->dl_stage) (void)hipHostFree(ctx->dl_stage);
     if (ctx->sp_mem) (void)hipFree(ctx->sp_mem);
-    if (ctx->exp_stream) { (void)hipStreamSynchronize(ctx->exp_stream); (void)hipStreamDestroy(ctx->exp_stream); }
     for (hipEvent_t e : ctx->exp_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->dl_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stage) { if (ctx->stage_pinned) (void)hipHostFree(ctx->stage); else std::free(ctx->stage); }
@@ -732,21 +648,10 @@ int landing_reserve(p265r_ctx* ctx, size_t need) {
     return P265R_OK;
 }
 
-// Sparse upload: expand the entries of nj jobs of class c (jobs, their begin words beg; their TBs are pool
-// elements [q0, q1)) into the coefficient pool, on stream xs.
-hipError_t launch_expand(hipStream_t xs, int16_t* d_pool, int c, const ResJob* jobs, int nj, size_t q0, size_t q1,
+// Sparse upload: expand the entries of nj jobs of class c (jobs, their begin words beg; their TBs start at pool
+// element q0) into the coefficient pool, on stream xs.
+hipError_t launch_expand(hipStream_t xs, int16_t* d_pool, int c, const ResJob* jobs, int nj, size_t q0,
                          const uint32_t* beg, const uint32_t* d_ent) {
-#if P265R_EXPAND_SCATTER
-    const hipError_t e = hipMemsetAsync(d_pool + q0, 0, sizeof(int16_t) * (q1 - q0), xs);
-    if (e != hipSuccess) return e;
-    switch (c) {
-        case RC_DST4: case RC_DCT4: case RC_TSKIP: coef_scatter_kernel<1><<<(nj + 255) / 256, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
-        case RC_DCT8: coef_scatter_kernel<4><<<(nj + 63) / 64, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
-        case RC_DCT16: coef_scatter_kernel<16><<<(nj + 15) / 16, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
-        default: coef_scatter_kernel<64><<<(nj + 3) / 4, 256, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
-    }
-#else
-    (void)q1;
     const int per_block = kExpandWaves * kExpandTile;    // int16 per block of a fixed-size class
     switch (c) {
         case RC_DST4: case RC_DCT4:
@@ -760,7 +665,6 @@ hipError_t launch_expand(hipStream_t xs, int16_t* d_pool, int c, const ResJob* j
         default:
             coef_expand_jobs_kernel<<<(unsigned)((nj + kExpandWaves - 1) / kExpandWaves), 64 * kExpandWaves, 0, xs>>>(d_pool, jobs, beg, d_ent, nj); break;
     }
-#endif
     return hipGetLastError();
 }
 
@@ -769,24 +673,10 @@ hipError_t launch_expand(hipStream_t xs, int16_t* d_pool, int c, const ResJob* j
 // chunk pack, copy and -- sparse -- expand on the device (coef_expand.h), then the header and the join.
 int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_coef* sp, int n_pics, p265r_batch** out) {
     if (!ctx || !pics || n_pics <= 0 || !out) return P265R_EINVAL;
-#if P265R_EXPERIMENTS
-    // P265R_UPLOAD_TIMES=1 (experiments build): wall time of the upload's stages on stderr
-    const bool ut = std::getenv("P265R_UPLOAD_TIMES") != nullptr;
-    std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> tp;
-#define P265R_UT_AT(name, t) do { if (ut) tp.emplace_back(name, t); } while (0)
-#else
-#define P265R_UT_AT(name, t) do { } while (0)
-#endif
-#define P265R_UT(name) P265R_UT_AT(name, std::chrono::steady_clock::now())
-    P265R_UT("start");
     *out = nullptr;
     UploadPlan plan;
-    std::chrono::steady_clock::time_point counted;
-    if (const int rc = plan_upload(ctx->params, ctx->geo, ctx->n_ctus, ctx->xg, ctx->split != 0, ctx->num_cus, pics, sp, n_pics, &plan,
-                                   P265R_EXPERIMENTS ? &counted : nullptr))
+    if (const int rc = plan_upload(ctx->params, ctx->geo, ctx->n_ctus, ctx->xg, ctx->split != 0, ctx->num_cus, pics, sp, n_pics, &plan))
         return rc;
-    P265R_UT_AT("validate+count", counted);
-    P265R_UT("layout");
     (void)hipSetDevice(ctx->device);
     if (const int rc = stage_reserve(ctx, plan.stage_need)) return rc;
     unsigned char* host = ctx->stage;
@@ -824,7 +714,6 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
     b->view.ctus0 = reinterpret_cast<const p265r_ctu*>(dbase + plan.o_ctus);
     b->view.err = b->d_err;
     b->h_pics.resize(n_pics);
-    P265R_UT("alloc");
 
     // Packing and H2D overlap: the pictures go in chunks, and a chunk's copies (UploadPlan::chunk_copies) are
     // enqueued as soon as it is packed, so the DMA engine copies chunk k while the host packs chunk k + 1.
@@ -839,23 +728,16 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
     };
     if (e == hipSuccess) e = hipMemsetAsync(dbase + plan.o_res, 0, plan.o_ijobs - plan.o_res, st);   // residual pool, job lists
     if (e == hipSuccess) e = hipMemsetAsync(dbase + plan.o_ijobs, 0, plan.o_rec - plan.o_ijobs, st);
-    // sparse: the expand kernels of a chunk follow its copies -- on the same stream, or (P265R_EXPAND_STREAM) on
-    // a second one behind an event, beside the next chunk's copies; with timing on, an event pair per chunk
+    // sparse: the expand kernels of a chunk follow its copies on the same stream; with timing on, inside an
+    // event pair per chunk
     const uint32_t* d_ent = reinterpret_cast<const uint32_t*>(d_sp);
     const uint32_t* d_beg = sp ? reinterpret_cast<const uint32_t*>(d_sp + (plan.s_beg - plan.s_ent)) : nullptr;
-    hipStream_t xs = st;
     const bool time_expand = sp && ctx->timing;
-    enum { EV_JOIN = 16, EV_TIMED = 17, EV_NUM = 17 + 32 };      // [k]: chunk k's gate; [EV_TIMED + 2 k (+ 1)]: its timed pair
-    auto expand_event = [&](int idx) -> hipEvent_t {
-        if (ctx->exp_ev.empty()) ctx->exp_ev.resize(EV_NUM, nullptr);
-        if (!ctx->exp_ev[idx] && e == hipSuccess)
-            e = idx >= EV_TIMED ? hipEventCreate(&ctx->exp_ev[idx]) : hipEventCreateWithFlags(&ctx->exp_ev[idx], hipEventDisableTiming);
+    auto expand_event = [&](int idx) -> hipEvent_t {             // [2 k], [2 k + 1]: chunk k's timed pair
+        if (ctx->exp_ev.size() <= (size_t)idx) ctx->exp_ev.resize((size_t)idx + 1, nullptr);
+        if (!ctx->exp_ev[idx] && e == hipSuccess) e = hipEventCreate(&ctx->exp_ev[idx]);
         return ctx->exp_ev[idx];
     };
-    if (sp && P265R_EXPAND_STREAM) {
-        if (!ctx->exp_stream && e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->exp_stream, hipStreamNonBlocking);
-        if (ctx->exp_stream) xs = ctx->exp_stream;
-    }
     ctx->last_expand_ms = -1.0;
     for (int k = 0; k < plan.n_chunks; ++k) {
         const int p0 = plan.chunk_lo(k), p1 = plan.chunk_lo(k + 1);
@@ -863,26 +745,15 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
         if (sp) close_chunk(plan, k, host);
         for (const H2dCopy& c : plan.chunk_copies(k)) h2d(c);
         if (!sp) continue;
-        if (xs != st) {
-            hipEvent_t gate = expand_event(k);
-            if (e == hipSuccess) e = hipEventRecord(gate, st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(xs, gate, 0);
-        }
-        if (time_expand) { hipEvent_t t0 = expand_event(EV_TIMED + 2 * k); if (e == hipSuccess) e = hipEventRecord(t0, xs); }
+        if (time_expand) { hipEvent_t t0 = expand_event(2 * k); if (e == hipSuccess) e = hipEventRecord(t0, st); }
         for (int c = 0; c < RC_NUM && e == hipSuccess; ++c) {
             const size_t j0 = (size_t)plan.job_at[p0][c];
             const int nj = plan.job_at[p1][c] - plan.job_at[p0][c];
-            if (nj) e = launch_expand(xs, b->d_pool, c, b->d_jobs[c] + j0, nj, plan.pool_at[p0][c], plan.pool_at[p1][c],
+            if (nj) e = launch_expand(st, b->d_pool, c, b->d_jobs[c] + j0, nj, plan.pool_at[p0][c],
                                       d_beg + plan.beg_kc[k * RC_NUM + c], d_ent);
         }
-        if (time_expand) { hipEvent_t t1 = expand_event(EV_TIMED + 2 * k + 1); if (e == hipSuccess) e = hipEventRecord(t1, xs); }
+        if (time_expand) { hipEvent_t t1 = expand_event(2 * k + 1); if (e == hipSuccess) e = hipEventRecord(t1, st); }
     }
-    if (xs != st) {                                              // the upload's stream waits for the last expand
-        hipEvent_t join = expand_event(EV_JOIN);
-        if (e == hipSuccess) e = hipEventRecord(join, xs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
-    }
-    P265R_UT("pack");
     // alignment gaps between the arrays and the coefficient pool's pad: zero on the device, as the device
     // image always had them; then the DevPic table and the error word (complete before returning: the
     // staging buffer is refilled by the next upload)
@@ -900,39 +771,210 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
                 b->h2d_bytes += wd * pb * ht;
             }
     }
-    P265R_UT("enqueue");
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    P265R_UT("h2d");
     if (time_expand && e == hipSuccess) {
         double ms = 0;
         for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
             float t = 0;
-            e = hipEventElapsedTime(&t, ctx->exp_ev[EV_TIMED + 2 * k], ctx->exp_ev[EV_TIMED + 2 * k + 1]);
+            e = hipEventElapsedTime(&t, ctx->exp_ev[2 * k], ctx->exp_ev[2 * k + 1]);
             ms += t;
         }
         if (e == hipSuccess) ctx->last_expand_ms = ms;
     }
-#if P265R_EXPERIMENTS
-    if (ut) {
-        fprintf(stderr, "[p265r] %s upload %d pictures, %.1f MB copied:", sp ? "sparse" : "dense", n_pics, (double)b->h2d_bytes / 1e6);
-        for (size_t i = 1; i < tp.size(); ++i)
-            fprintf(stderr, " %s %.2f ms", tp[i].first, std::chrono::duration<double, std::milli>(tp[i].second - tp[i - 1].second).count());
-        fprintf(stderr, "\n");
-    }
-#endif
-#undef P265R_UT
-#undef P265R_UT_AT
     if (e != hipSuccess) {
         // copies (and expand kernels) enqueued before the failing call may still be in flight: let them end
         // before the allocation they write is freed
         int rc = hip_fail(e, "upload");
         (void)hipStreamSynchronize(st);
-        if (xs != st) (void)hipStreamSynchronize(xs);
         (void)hipFree(b->mem);
         delete b;
         return rc;
     }
     *out = b;
+    return P265R_OK;
+}
+
+// Stream plan of one run (no phase timing):
+// * a batch smaller than the chip (< 1 picture per CU: tile units, decoder batches, a few workgroups
+//   per launch) keeps every phase on its lane stream, and such batches run side by side: extra prep /
+//   residual streams would outnumber the hardware queues (4 by default) and put one lane's kernels
+//   behind another's (C5, 4 lanes: 2.3 M CTU/s forked vs 3.0 M unforked; 5.2 M unforked at
+//   GPU_MAX_HW_QUEUES=8, round 4);
+// * a chip-filling batch forks its prep kernel onto the lane's prep stream (P265R_FORK_PREP, default on);
+// * P265R_PHASE_ORDER builds: a chip-filling batch in a pipelined context runs in PHASE ORDER: its residual +
+//   prep phase (on two streams of the lane's own) waits for the last intra launch of ANY lane and runs beside
+//   the previous batch's loop filters; its intra phase waits for the last loop-filter launch, so the row
+//   kernel (W = 12, all of every CU's registers) always runs alone -- overlapping it with the other
+//   phases cost as much as it hid (3 lanes unordered = serial, 43.0 vs 43.5 M CTU/s, round 4);
+// * P265R_EARLY_RESIDUAL builds: otherwise (a lone lane's re-runs) the EARLY residual phase: residual + prep
+//   start when this batch's previous intra phase ends, beside its previous loop filters.
+struct RunPlan {
+    bool recon;            // not a recon-input batch: the residual and intra phases run
+    bool prep;             // ... on the row pipeline: the job prep kernel runs
+    bool fork;             // ... on the lane's prep stream (ctx->aux) instead of the lane stream
+    bool ordered, early;   // the two check-variant schedules
+    hipEvent_t after;      // ordered / early: the event the residual + prep phase starts behind, on streams of
+                           // its own (the residual kernels on ctx->aux2), instead of in the lane stream's order
+};
+
+RunPlan plan_run(const p265r_ctx* ctx, const p265r_batch* b) {
+    RunPlan rp{};
+    rp.recon = !b->recon_input;
+    rp.prep = rp.recon && ctx->schedule == 1;
+    const bool big = b->n_pics >= ctx->num_cus;
+    rp.fork = rp.prep && big && ctx->fork_prep;
+    rp.ordered = P265R_PHASE_ORDER && ctx->pipeline > 1 && rp.fork && !ctx->timing;
+    rp.early = !rp.ordered && P265R_EARLY_RESIDUAL && rp.fork && !ctx->timing && b->intra_done;
+    rp.after = rp.ordered ? (ctx->last_intra_valid ? ctx->last_intra_ev : nullptr) : (rp.early ? b->intra_done : nullptr);
+    return rp;
+}
+
+// Entry li of a per-lane list of second streams (ctx->aux, ctx->aux2) exists, with its entry of each event list
+// (created on first use).
+int lane_stream_reserve(std::vector<hipStream_t>& streams, std::initializer_list<std::vector<hipEvent_t>*> events, size_t li) {
+    if (streams.size() <= li) {
+        streams.resize(li + 1, nullptr);
+        for (auto* ev : events) ev->resize(li + 1, nullptr);
+    }
+    if (!streams[li]) {
+        HIP_TRY(hipStreamCreateWithFlags(&streams[li], hipStreamNonBlocking));
+        for (auto* ev : events) HIP_TRY(hipEventCreateWithFlags(&(*ev)[li], hipEventDisableTiming));
+    }
+    return P265R_OK;
+}
+
+// Phase 1 of a run: the residual kernels (one per job class), the intra job prep and the deblocking edge map;
+// the lane stream s continues behind all of them.
+int run_residual_prep(p265r_ctx* ctx, p265r_batch* b, const Geo& g, const RunPlan& rp, p265r_timings* tm) {
+    hipStream_t s = b->stream;
+    const size_t li = (size_t)b->lane;
+    const int bdl = g.bd[0], bdc = g.bd[1];
+    const uint8_t* sf = ctx->params.scaling_list_enabled ? ctx->d_sf : nullptr;
+    // ordered / early: behind rp.after, and behind the batch's own previous intra phase (the last reader of its
+    // residual pool and job lists): rp.after is the last intra launch of ANY lane, which only orders after it
+    // when every intra launch of the context ran phase-ordered (a small or timed batch on another lane does not)
+    auto start_after = [&](hipStream_t st) -> int {
+        HIP_TRY(hipStreamWaitEvent(st, rp.after, 0));
+        if (b->intra_done && rp.after != b->intra_done) HIP_TRY(hipStreamWaitEvent(st, b->intra_done, 0));
+        return P265R_OK;
+    };
+    hipStream_t rs = s;                              // the residual kernels' stream
+    if (rp.after) {
+        if (int rc = lane_stream_reserve(ctx->aux2, {&ctx->join2_ev}, li)) return rc;
+        rs = ctx->aux2[li];
+        if (int rc = start_after(rs)) return rc;
+    }
+    hipStream_t ps = s;                              // the prep kernel's stream
+    if (rp.fork) {
+        if (int rc = lane_stream_reserve(ctx->aux, {&ctx->fork_ev, &ctx->join_ev}, li)) return rc;
+        ps = ctx->aux[li];
+        if (rp.after) {
+            if (int rc = start_after(ps)) return rc;
+        } else {
+            HIP_TRY(hipEventRecord(ctx->fork_ev[li], s));
+            HIP_TRY(hipStreamWaitEvent(ps, ctx->fork_ev[li], 0));
+        }
+    }
+    if (rp.prep) {
+        // intra job preparation (availability, filter decisions, Cb/Cr pairing): independent
+        // of the residuals, timed with the residual phase; enqueued first so that, forked, its
+        // waves start before the residual kernels fill the chip
+        // (tr_info: launch_rows' latency layouts, the cross-group kernel and the W = 16 split, need 2 n_pics <= CUs)
+        Geo gp = g;
+        gp.tr_info = 2 * (long long)b->n_pics <= ctx->num_cus ? 1 : 0;
+        intra_prep_kernel<<<dim3(g.wc, g.hc, b->n_pics), 64, 0, ps>>>(b->d_pics, gp, b->view);
+        ++tm->residual_launches;
+        if (ps != s) HIP_TRY(hipEventRecord(ctx->join_ev[li], ps));
+    }
+    // (scaling lists: the SL instances, which read m from the context's ScalingFactor table)
+#define P265R_RES_LAUNCH(K, KSL, blocks, ...)                                                                     \
+    do {                                                                                                          \
+        if (sf) KSL<<<(blocks), 256, 0, rs>>>(__VA_ARGS__, sf);                                                   \
+        else K<<<(blocks), 256, 0, rs>>>(__VA_ARGS__, nullptr);                                                   \
+        ++tm->residual_launches;                                                                                  \
+    } while (0)
+    if (rp.recon && b->n_jobs[RC_DST4])
+        P265R_RES_LAUNCH((residual4_kernel<true, false>), (residual4_kernel<true, true>), (b->n_jobs[RC_DST4] + 255) / 256,
+                         b->d_pool, b->d_res, b->d_jobs[RC_DST4], b->n_jobs[RC_DST4], bdl, b->slab[RC_DST4]);
+    if (rp.recon && b->n_jobs[RC_DCT4])
+        P265R_RES_LAUNCH((residual4_kernel<false, false>), (residual4_kernel<false, true>), (b->n_jobs[RC_DCT4] + 255) / 256,
+                         b->d_pool, b->d_res, b->d_jobs[RC_DCT4], b->n_jobs[RC_DCT4], bdc, b->slab[RC_DCT4]);
+    if (rp.recon && b->n_jobs[RC_DCT8])
+        P265R_RES_LAUNCH((residualN_kernel<3, false>), (residualN_kernel<3, true>), (b->n_jobs[RC_DCT8] + 31) / 32,
+                         b->d_pool, b->d_res, b->d_jobs[RC_DCT8], b->n_jobs[RC_DCT8], bdl, bdc, b->slab[RC_DCT8]);
+    if (rp.recon && b->n_jobs[RC_DCT16])
+        P265R_RES_LAUNCH((residualN_kernel<4, false>), (residualN_kernel<4, true>), (b->n_jobs[RC_DCT16] + 15) / 16,
+                         b->d_pool, b->d_res, b->d_jobs[RC_DCT16], b->n_jobs[RC_DCT16], bdl, bdc, b->slab[RC_DCT16]);
+    if (rp.recon && b->n_jobs[RC_DCT32])
+        P265R_RES_LAUNCH((residualN_kernel<5, false>), (residualN_kernel<5, true>), (b->n_jobs[RC_DCT32] + 7) / 8,
+                         b->d_pool, b->d_res, b->d_jobs[RC_DCT32], b->n_jobs[RC_DCT32], bdl, bdc, b->slab[RC_DCT32]);
+#undef P265R_RES_LAUNCH
+    if (rp.recon && b->n_jobs[RC_TSKIP]) {
+        residual_tskip_kernel<<<(b->n_jobs[RC_TSKIP] + 255) / 256, 256, 0, rs>>>(b->d_pool, b->d_res, b->d_jobs[RC_TSKIP], b->n_jobs[RC_TSKIP], bdl, bdc, sf);
+        ++tm->residual_launches;
+    }
+    if (ps != s) HIP_TRY(hipStreamWaitEvent(s, ctx->join_ev[li], 0));
+    if (rs != s) {
+        HIP_TRY(hipEventRecord(ctx->join2_ev[li], rs));
+        HIP_TRY(hipStreamWaitEvent(s, ctx->join2_ev[li], 0));
+    }
+    if (b->dbk) {
+        // deblocking edge / QpY map: depends on the records only
+        if (g.pel16) dbk_map_kernel<uint16_t><<<dim3(ctx->n_ctus, b->n_pics), 64, 0, s>>>(b->d_pics, g);
+        else dbk_map_kernel<uint8_t><<<dim3(ctx->n_ctus, b->n_pics), 64, 0, s>>>(b->d_pics, g);   // (context-size grid)
+        ++tm->residual_launches;
+    }
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// Phase 2 of a run: the intra wavefront on the lane stream -- the row pipeline, or one launch per anti-diagonal.
+int run_intra(p265r_ctx* ctx, p265r_batch* b, const Geo& g, const RunPlan& rp, p265r_timings* tm) {
+    hipStream_t s = b->stream;
+    if (rp.recon && ctx->schedule == 1) {
+        // per-CU workgroup slots cleared per run; the error word (d_err[0]) is sticky from upload on,
+        // so p265r_batch_status / p265r_batch_download report a give-up in ANY run of the batch
+        // (and the cross-group kernel's progress words behind them)
+        HIP_TRY(hipMemsetAsync(b->d_err + 64, 0, kRowCuSlots * 16 + (b->d_xg_prog ? sizeof(int) * 2 * ((size_t)g.hc + 1) * b->n_pics : 0), s));
+        if (rp.ordered && ctx->last_lf_valid) HIP_TRY(hipStreamWaitEvent(s, ctx->last_lf_ev, 0));
+        // does another lane have a run enqueued that the API has not synchronised since?  (host
+        // state only, so the build a run gets is a function of the call sequence)
+        // (phase order: the intra phase has the GPU to itself by construction)
+        const bool alone = rp.ordered || (ctx->lane_busy & ~(1u << b->lane)) == 0u;
+        if (int rc = launch_rows(ctx, b, s, alone)) return rc;
+        ++tm->intra_launches;
+    }
+    const int n_steps = (rp.recon && ctx->schedule == 0) ? (g.wc - 1) + 2 * (g.hc - 1) + 1 : 0;
+    for (int step = 0; step < n_steps; ++step) {
+        const int d = step - (g.wc - 1);
+        const int cy_min = d > 0 ? (d + 1) / 2 : 0;
+        const int cy_max = std::min(g.hc - 1, step / 2);
+        if (cy_max < cy_min) continue;
+        dim3 grid(cy_max - cy_min + 1, b->n_pics);
+        if (g.pel16) intra_step_kernel<uint16_t><<<grid, 64, 0, s>>>(b->d_pics, b->d_pool, b->d_res, g, step, cy_min);
+        else intra_step_kernel<uint8_t><<<grid, 64, 0, s>>>(b->d_pics, b->d_pool, b->d_res, g, step, cy_min);
+        ++tm->intra_launches;
+    }
+    HIP_TRY(hipGetLastError());
+    if (rp.recon) {                                  // the residual pool and job lists are free again
+        if (!b->intra_done) HIP_TRY(hipEventCreateWithFlags(&b->intra_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b->intra_done, s));
+        if (!ctx->last_intra_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->last_intra_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ctx->last_intra_ev, s));
+        ctx->last_intra_valid = true;
+    }
+    return P265R_OK;
+}
+
+// Phase 3 of a run: the in-loop filters (deblocking + SAO) on the lane stream.
+int run_loop_filters(p265r_ctx* ctx, p265r_batch* b, const Geo& g, const RunPlan& rp, p265r_timings* tm) {
+    hipStream_t s = b->stream;
+    if (int rc = launch_loop_filters(ctx, b, g, s, &tm->sao_launches)) return rc;
+    if (rp.ordered) {                                // the next batch's intra phase starts after this
+        if (!ctx->last_lf_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->last_lf_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ctx->last_lf_ev, s));
+        ctx->last_lf_valid = true;
+    }
     return P265R_OK;
 }
 
@@ -972,212 +1014,17 @@ int p265r_batch_run(p265r_ctx* ctx, p265r_batch* b) {
         }
         HIP_TRY(hipEventRecord(ev[0], s));
     }
-    // ---- residual phase ----------------------------------------------------------
-    const int bdl = g.bd[0], bdc = g.bd[1];
-    const bool recon = !b->recon_input;
-    // timing experiments only (P265R_SKIP bit 0: residual kernels, bit 1: job preparation, bit 2:
-    // loop filters) on RE-RUNS of a resident batch: its residuals / job lists from the previous
-    // run are still in place, so the output is unchanged while the skipped phase costs nothing
-    const int skip = b->runs > 0 ? ctx->skip : 0;
     if (ctx->params.scaling_list_enabled && !ctx->d_sf && !b->recon_input) return P265R_ESTATE;   // factors not set
-    const uint8_t* sf = ctx->params.scaling_list_enabled ? ctx->d_sf : nullptr;
     ++b->runs;
     ctx->lane_busy |= 1u << b->lane;
-    const bool prep = recon && ctx->schedule == 1 && !(skip & 2);
-    hipStream_t ps = s;                              // the prep kernel's stream
-    // Stream plan of one run (no phase timing):
-    // * a batch smaller than the chip (< 1 picture per CU: tile units, decoder batches, a few workgroups
-    //   per launch) keeps every phase on its lane stream, and such batches run side by side: extra prep /
-    //   residual streams would outnumber the hardware queues (4 by default) and put one lane's kernels
-    //   behind another's (C5, 4 lanes: 2.3 M CTU/s forked vs 3.0 M unforked; 5.2 M unforked at
-    //   GPU_MAX_HW_QUEUES=8, round 4);
-    // * a chip-filling batch in a pipelined context runs in PHASE ORDER: its residual + prep phase (on
-    //   two streams of the lane's own) waits for the last intra launch of ANY lane and runs beside the
-    //   previous batch's loop filters; its intra phase waits for the last loop-filter launch, so the row
-    //   kernel (W = 12, all of every CU's registers) always runs alone -- overlapping it with the other
-    //   phases cost as much as it hid (3 lanes unordered = serial, 43.0 vs 43.5 M CTU/s, round 4);
-    // * otherwise (a lone lane's re-runs) the EARLY residual phase: residual + prep start when this
-    //   batch's previous intra phase ends, beside its previous loop filters.
-    const bool big = b->n_pics >= ctx->num_cus;
-    // P265R_SAO_AUX: the loop filters of this run go to the lane's aux stream (after its intra phase), the
-    // prep kernel stays on the lane, so the next run's residual + prep phase overlaps this run's loop filters
-    const bool sao_aux = P265R_SAO_AUX && !P265R_PHASE_ORDER && !P265R_EARLY_RESIDUAL && ctx->pipeline > 1 && big && prep &&
-                         !ctx->timing && ctx->fork_prep == 1 && (b->sao || b->dbk) && !(skip & 4);
-    const int fork_prep = big && !sao_aux ? ctx->fork_prep : 0;
-    const bool ordered = P265R_PHASE_ORDER && ctx->pipeline > 1 && prep && fork_prep == 1 && !ctx->timing;
-    const bool early = !ordered && P265R_EARLY_RESIDUAL && prep && fork_prep == 1 && !ctx->timing && b->intra_done &&
-                       !(skip & 1);
-    hipEvent_t r_after = ordered ? (ctx->last_intra_valid ? ctx->last_intra_ev : nullptr) : (early ? b->intra_done : nullptr);
-    if (ordered && ctx->order_r == 0) r_after = b->intra_done;     // (A/B: residual phase not held back)
-    hipStream_t rs = s;                              // the residual kernels' stream
-    if ((ordered || early) && r_after) {
-        const size_t li = (size_t)b->lane;
-        if (ctx->aux2.size() <= li) { ctx->aux2.resize(li + 1, nullptr); ctx->join2_ev.resize(li + 1, nullptr); }
-        if (!ctx->aux2[li]) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->aux2[li], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->join2_ev[li], hipEventDisableTiming));
-        }
-        rs = ctx->aux2[li];
-        HIP_TRY(hipStreamWaitEvent(rs, r_after, 0));
-        // the batch's own previous intra phase (the last reader of its residual pool and job lists):
-        // r_after is the last intra launch of ANY lane, which only orders after it when every intra
-        // launch of the context ran phase-ordered (a small or timed batch on another lane does not)
-        if (b->intra_done && r_after != b->intra_done) HIP_TRY(hipStreamWaitEvent(rs, b->intra_done, 0));
-    }
-    if (prep && fork_prep) {
-        // fork_prep 2: one prep stream shared by all lanes (fewer streams than HW queues, so no
-        // lane's intra kernel sits in front of a prep kernel in a shared hardware queue)
-        const size_t li = fork_prep == 2 ? 0 : (size_t)b->lane;
-        if (ctx->aux.size() <= li) {
-            ctx->aux.resize(li + 1, nullptr); ctx->fork_ev.resize(li + 1, nullptr); ctx->join_ev.resize(li + 1, nullptr);
-        }
-        if (!ctx->aux[li]) {
-            if (ctx->stream_prio) {
-                int least = 0, greatest = 0;
-                HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                HIP_TRY(hipStreamCreateWithPriority(&ctx->aux[li], hipStreamNonBlocking, least));
-            } else {
-                HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[li], hipStreamNonBlocking));
-            }
-            HIP_TRY(hipEventCreateWithFlags(&ctx->fork_ev[li], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->join_ev[li], hipEventDisableTiming));
-        }
-        ps = ctx->aux[li];
-        if ((ordered || early) && r_after) {
-            HIP_TRY(hipStreamWaitEvent(ps, r_after, 0));
-            if (b->intra_done && r_after != b->intra_done) HIP_TRY(hipStreamWaitEvent(ps, b->intra_done, 0));
-        } else {
-            HIP_TRY(hipEventRecord(ctx->fork_ev[li], s));
-            HIP_TRY(hipStreamWaitEvent(ps, ctx->fork_ev[li], 0));
-        }
-    }
-    auto launch_prep = [&]() -> int {
-        // intra job preparation (availability, filter decisions, Cb/Cr pairing): independent
-        // of the residuals, timed with the residual phase; enqueued first so that, forked, its
-        // waves start before the residual kernels fill the chip
-        // (a superset of launch_rows' latency layouts: the cross-group kernel and the W = 16 split need
-        // 2 n_pics <= CUs, the experiments' fixed W = 16 any size)
-        Geo gp = g;
-        gp.tr_info = (2 * (long long)b->n_pics <= ctx->num_cus || ctx->row_waves == 16) ? 1 : 0;
-        intra_prep_kernel<<<dim3(g.wc, g.hc, b->n_pics), 64, ctx->prep_lds, ps>>>(b->d_pics, gp, b->view);
-        ++tm.residual_launches;
-        if (ps != s) HIP_TRY(hipEventRecord(ctx->join_ev[fork_prep == 2 ? 0 : (size_t)b->lane], ps));
-        return P265R_OK;
-    };
-    if (prep && !ctx->prep_last) { int rc = launch_prep(); if (rc) return rc; }
-    // (scaling lists: the SL instances, which read m from the context's ScalingFactor table)
-#define P265R_RES_LAUNCH(K, KSL, blocks, ...)                                                                     \
-    do {                                                                                                          \
-        if (sf) KSL<<<(blocks), 256, ctx->res_lds, rs>>>(__VA_ARGS__, sf);                                        \
-        else K<<<(blocks), 256, ctx->res_lds, rs>>>(__VA_ARGS__, nullptr);                                        \
-        ++tm.residual_launches;                                                                                   \
-    } while (0)
-    if (recon && !(skip & 1) && b->n_jobs[RC_DST4])
-        P265R_RES_LAUNCH((residual4_kernel<true, false>), (residual4_kernel<true, true>), (b->n_jobs[RC_DST4] + 255) / 256,
-                         b->d_pool, b->d_res, b->d_jobs[RC_DST4], b->n_jobs[RC_DST4], bdl, b->slab[RC_DST4]);
-    if (recon && !(skip & 1) && b->n_jobs[RC_DCT4])
-        P265R_RES_LAUNCH((residual4_kernel<false, false>), (residual4_kernel<false, true>), (b->n_jobs[RC_DCT4] + 255) / 256,
-                         b->d_pool, b->d_res, b->d_jobs[RC_DCT4], b->n_jobs[RC_DCT4], bdc, b->slab[RC_DCT4]);
-    if (recon && !(skip & 1) && b->n_jobs[RC_DCT8])
-        P265R_RES_LAUNCH((residualN_kernel<3, false>), (residualN_kernel<3, true>), (b->n_jobs[RC_DCT8] + 31) / 32,
-                         b->d_pool, b->d_res, b->d_jobs[RC_DCT8], b->n_jobs[RC_DCT8], bdl, bdc, b->slab[RC_DCT8]);
-    if (recon && !(skip & 1) && b->n_jobs[RC_DCT16])
-        P265R_RES_LAUNCH((residualN_kernel<4, false>), (residualN_kernel<4, true>), (b->n_jobs[RC_DCT16] + 15) / 16,
-                         b->d_pool, b->d_res, b->d_jobs[RC_DCT16], b->n_jobs[RC_DCT16], bdl, bdc, b->slab[RC_DCT16]);
-    if (recon && !(skip & 1) && b->n_jobs[RC_DCT32])
-        P265R_RES_LAUNCH((residualN_kernel<5, false>), (residualN_kernel<5, true>), (b->n_jobs[RC_DCT32] + 7) / 8,
-                         b->d_pool, b->d_res, b->d_jobs[RC_DCT32], b->n_jobs[RC_DCT32], bdl, bdc, b->slab[RC_DCT32]);
-#undef P265R_RES_LAUNCH
-    if (recon && !(skip & 1) && b->n_jobs[RC_TSKIP]) {
-        residual_tskip_kernel<<<(b->n_jobs[RC_TSKIP] + 255) / 256, 256, 0, rs>>>(b->d_pool, b->d_res, b->d_jobs[RC_TSKIP], b->n_jobs[RC_TSKIP], bdl, bdc, sf);
-        ++tm.residual_launches;
-    }
-    if (prep && ctx->prep_last) { int rc = launch_prep(); if (rc) return rc; }
-    if (prep && ps != s) HIP_TRY(hipStreamWaitEvent(s, ctx->join_ev[fork_prep == 2 ? 0 : (size_t)b->lane], 0));
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(ctx->join2_ev[(size_t)b->lane], rs));
-        HIP_TRY(hipStreamWaitEvent(s, ctx->join2_ev[(size_t)b->lane], 0));
-    }
-    if (b->dbk) {
-        // deblocking edge / QpY map: depends on the records only
-        if (g.pel16) dbk_map_kernel<uint16_t><<<dim3(ctx->n_ctus, b->n_pics), 64, 0, s>>>(b->d_pics, g);
-        else dbk_map_kernel<uint8_t><<<dim3(ctx->n_ctus, b->n_pics), 64, 0, s>>>(b->d_pics, g);   // (context-size grid)
-        ++tm.residual_launches;
-    }
-    HIP_TRY(hipGetLastError());
+    const RunPlan rp = plan_run(ctx, b);
+    if (int rc = run_residual_prep(ctx, b, g, rp, &tm)) return rc;
     if (ctx->debug_sync) { fprintf(stderr, "[p265r] residual phase enqueued\n"); HIP_TRY(hipStreamSynchronize(s)); fprintf(stderr, "[p265r] residual phase done\n"); }
     if (ctx->timing) HIP_TRY(hipEventRecord(ev[1], s));
-    // ---- intra wavefront ---------------------------------------------------------------
-    if (recon && ctx->schedule == 1) {
-        // per-CU workgroup slots cleared per run; the error word (d_err[0]) is sticky from upload on,
-        // so p265r_batch_status / p265r_batch_download report a give-up in ANY run of the batch
-        // (and the cross-group kernel's progress words behind them)
-        HIP_TRY(hipMemsetAsync(b->d_err + 64, 0, kRowCuSlots * 16 + (b->d_xg_prog ? sizeof(int) * 2 * ((size_t)g.hc + 1) * b->n_pics : 0), s));
-        // the previous run's loop filters (on the aux stream) read the planes this run writes
-        if (b->sao_pending) { HIP_TRY(hipStreamWaitEvent(s, b->sao_done, 0)); b->sao_pending = false; }
-        if (ordered && ctx->last_lf_valid) HIP_TRY(hipStreamWaitEvent(s, ctx->last_lf_ev, 0));
-        // does another lane have a run enqueued that the API has not synchronised since?  (host
-        // state only, so the build a run gets is a function of the call sequence)
-        // (phase order: the intra phase has the GPU to itself by construction)
-        bool alone = ordered || (ctx->lane_busy & ~(1u << b->lane)) == 0u;
-#ifdef P265R_ALONE_PIPE
-        alone = alone && ctx->pipeline == 1;       // A/B: a pipelined context never runs the W = 12 build
-#endif
-        int rc = launch_rows(ctx, b, s, alone);
-        if (rc) return rc;
-        ++tm.intra_launches;
-    }
-    const int n_steps = (recon && ctx->schedule == 0) ? (g.wc - 1) + 2 * (g.hc - 1) + 1 : 0;
-    for (int step = 0; step < n_steps; ++step) {
-        const int d = step - (g.wc - 1);
-        const int cy_min = d > 0 ? (d + 1) / 2 : 0;
-        const int cy_max = std::min(g.hc - 1, step / 2);
-        if (cy_max < cy_min) continue;
-        dim3 grid(cy_max - cy_min + 1, b->n_pics);
-        if (g.pel16) intra_step_kernel<uint16_t><<<grid, 64, 0, s>>>(b->d_pics, b->d_pool, b->d_res, g, step, cy_min);
-        else intra_step_kernel<uint8_t><<<grid, 64, 0, s>>>(b->d_pics, b->d_pool, b->d_res, g, step, cy_min);
-        ++tm.intra_launches;
-    }
-    HIP_TRY(hipGetLastError());
-    if (recon) {                                     // the residual pool and job lists are free again
-        if (!b->intra_done) HIP_TRY(hipEventCreateWithFlags(&b->intra_done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(b->intra_done, s));
-        if (!ctx->last_intra_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->last_intra_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ctx->last_intra_ev, s));
-        ctx->last_intra_valid = true;
-    }
+    if (int rc = run_intra(ctx, b, g, rp, &tm)) return rc;
     if (ctx->debug_sync) { fprintf(stderr, "[p265r] intra phase enqueued\n"); HIP_TRY(hipStreamSynchronize(s)); fprintf(stderr, "[p265r] intra phase done\n"); }
     if (ctx->timing) HIP_TRY(hipEventRecord(ev[2], s));
-    // ---- in-loop filters: deblocking + SAO ----------------------------------------------
-    const hipStream_t lane_s = s;
-    if (sao_aux) {
-        const size_t li = (size_t)b->lane;
-        if (ctx->aux.size() <= li) {
-            ctx->aux.resize(li + 1, nullptr); ctx->fork_ev.resize(li + 1, nullptr); ctx->join_ev.resize(li + 1, nullptr);
-        }
-        if (!ctx->aux[li]) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[li], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->fork_ev[li], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->join_ev[li], hipEventDisableTiming));
-        }
-        if (!b->sao_done) HIP_TRY(hipEventCreateWithFlags(&b->sao_done, hipEventDisableTiming));
-        s = ctx->aux[li];
-        HIP_TRY(hipStreamWaitEvent(s, b->intra_done, 0));
-    }
-    if (!(skip & 4)) {
-        int rc = launch_loop_filters(ctx, b, g, s, &tm.sao_launches);
-        if (rc) return rc;
-    }
-    if (sao_aux) {
-        HIP_TRY(hipEventRecord(b->sao_done, s));
-        b->sao_pending = true;
-        s = lane_s;
-    }
-    if (ordered) {                                   // the next batch's intra phase starts after this
-        if (!ctx->last_lf_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->last_lf_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ctx->last_lf_ev, s));
-        ctx->last_lf_valid = true;
-    }
+    if (int rc = run_loop_filters(ctx, b, g, rp, &tm)) return rc;
     if (ctx->timing) {
         HIP_TRY(hipEventRecord(ev[3], s));
         p265r_ctx::Run run;
@@ -1192,7 +1039,6 @@ int p265r_batch_run(p265r_ctx* ctx, p265r_batch* b) {
 int p265r_batch_download(p265r_ctx* ctx, p265r_batch* b, const p265r_picture* pics, int n_pics) {
     if (!ctx || !b || !pics || n_pics != b->n_pics) return P265R_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     const Geo& g = ctx->geo;
     // planes to copy: (host destination, device source, row pitch, width, height)
     struct Item { void* dst; const unsigned char* src; int pitch, w, h; size_t bytes; };
@@ -1264,7 +1110,6 @@ int p265r_batch_download(p265r_ctx* ctx, p265r_batch* b, const p265r_picture* pi
 int p265r_batch_status(p265r_ctx* ctx, p265r_batch* b) {
     if (!ctx || !b) return P265R_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     // the lane is idle now (every run on it, of any batch, has completed)
     ctx->lane_busy &= ~(1u << b->lane);
@@ -1284,7 +1129,6 @@ int p265r_batch_status(p265r_ctx* ctx, p265r_batch* b) {
 int p265r_batch_digest(p265r_ctx* ctx, p265r_batch* b, int which, uint64_t* out, int n) {
     if (!ctx || !b || !out || n != 3 * b->n_pics || (which != 0 && which != 1)) return P265R_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     // after every run enqueued on the batch's lane (stream order); one device buffer per call
     unsigned long long* d = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), sizeof(uint64_t) * (size_t)n));
@@ -1304,7 +1148,6 @@ int p265r_batch_digest(p265r_ctx* ctx, p265r_batch* b, int which, uint64_t* out,
 int p265r_batch_digest_async(p265r_ctx* ctx, p265r_batch* b, int which, int slot) {
     if (!ctx || !b || (which != 0 && which != 1) || slot < 0 || slot >= P265R_DIGEST_SLOTS) return P265R_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     const size_t per_slot = sizeof(uint64_t) * 3 * (size_t)b->n_pics;
     if (!b->d_dig) {
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_dig), per_slot * P265R_DIGEST_SLOTS));
@@ -1323,7 +1166,6 @@ int p265r_batch_digest_slots(p265r_ctx* ctx, p265r_batch* b, uint64_t* out, int 
     if (!ctx || !b || !out || n_slots < 1 || n_slots > P265R_DIGEST_SLOTS) return P265R_EINVAL;
     if (!b->d_dig) return P265R_ESTATE;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     HIP_TRY(hipMemcpyAsync(out, b->d_dig, sizeof(uint64_t) * 3 * (size_t)b->n_pics * n_slots, hipMemcpyDeviceToHost,
                            b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1335,7 +1177,6 @@ int p265r_batch_hash_async(p265r_ctx* ctx, p265r_batch* b, int hash_type) {
     if (hash_type != P265R_HASH_MD5 && hash_type != P265R_HASH_CRC && hash_type != P265R_HASH_CHECKSUM) return P265R_EINVAL;
     if (b->runs == 0) return P265R_ESTATE;                  // (no output planes yet, as for p265r_batch_export)
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     const int n_planes = 3 * b->n_pics;
     const size_t out_bytes = 16 * (size_t)n_planes, acc_bytes = sizeof(uint32_t) * (size_t)n_planes;
     if (!b->d_hash) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_hash), out_bytes + acc_bytes));
@@ -1361,7 +1202,6 @@ int p265r_batch_hash_read(p265r_ctx* ctx, p265r_batch* b, uint8_t* out, int n_by
     if (!ctx || !b || !out || (long long)n_bytes != 48ll * b->n_pics) return P265R_EINVAL;
     if (!b->d_hash) return P265R_ESTATE;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_sao(b)) return rc;
     HIP_TRY(hipMemcpyAsync(out, b->d_hash, (size_t)n_bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return p265r_batch_status(ctx, b);
@@ -1421,7 +1261,6 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
     if (need > dst_bytes) return P265R_ERANGE;
     if (!on_device(static_cast<const unsigned char*>(dev_dst) + need - 1)) return P265R_EINVAL;
     // ---- enqueue ---------------------------------------------------------------------------------
-    if (int rc = join_sao(b)) return rc;
     ExportArgs a{};
     a.dst = static_cast<uint8_t*>(dev_dst);
     a.frame_bytes = desc->frame_bytes;
@@ -1450,13 +1289,11 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
 int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (!ctx || !b) return P265R_EINVAL;
     (void)hipSetDevice(ctx->device);
-    (void)join_sao(b);
     if (ctx->pending == b) ctx->pending = nullptr;
     // its lane may still run it: the allocation is reused by the next upload (another stream); the
     // lane stream's last run waited for every residual / prep kernel of the batch
     hipError_t e = b->stream ? hipStreamSynchronize(b->stream) : hipSuccess;
     if (b->intra_done) (void)hipEventDestroy(b->intra_done);
-    if (b->sao_done) (void)hipEventDestroy(b->sao_done);
     if (b->d_dig) (void)hipFree(b->d_dig);
     if (b->d_hash) (void)hipFree(b->d_hash);
     for (void* p : b->exp_idx) (void)hipFree(p);
@@ -1513,7 +1350,7 @@ int p265r_set_pipeline(p265r_ctx* ctx, int depth) {
     HIP_TRY(hipSetDevice(ctx->device));
     while ((int)ctx->lanes.size() < depth) {
         hipStream_t st = nullptr;
-        HIP_TRY(lane_stream_create(ctx, &st));
+        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         ctx->lanes.push_back(st);
     }
     ctx->pipeline = depth;
@@ -1550,16 +1387,18 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
                                      "CU: component split, W=16); otherwise W=12 while no other "
                                      "lane has a run enqueued since the API synchronised it, else pipe_waves (W=8, 80 VGPRs: "
                                      "the other lanes' residual / prep / SAO waves fit beside it)"),
-        ctx->lean, g.fair, g.quad, ctx->luma_lead, ctx->sao_rows, ctx->skip, ctx->debug_sync ? 1 : 0,
-        ctx->pipeline, ctx->fork_prep, ctx->pipe_waves, hwq_env(), ctx->num_cus,
+        // (the keys of retired knobs stay, with the value that was kept: lean 1, skip 0, pipe_waves 8,
+        // experiments_build 0, row_launches.other 0, sparse_expand "lds tile", sparse_expand_stream 0)
+        1, g.fair, g.quad, ctx->luma_lead, ctx->sao_rows, 0, ctx->debug_sync ? 1 : 0,
+        ctx->pipeline, ctx->fork_prep, 8, hwq_env(), ctx->num_cus,
 #ifdef P265R_DEBUG_DIAG
         1,
 #else
         0,
 #endif
-        P265R_EXPERIMENTS, ctx->split, ctx->last_split ? 1 : 0, ctx->xg, ctx->last_xg ? 1 : 0, P265R_PHASE_ORDER, P265R_EARLY_RESIDUAL,
-        (int)ctx->params.bit_depth_luma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], ctx->row_launches[4],
-        P265R_EXPAND_SCATTER ? "memset + global scatter" : "lds tile", P265R_EXPAND_STREAM, ctx->last_expand_ms,
+        0, ctx->split, ctx->last_split ? 1 : 0, ctx->xg, ctx->last_xg ? 1 : 0, P265R_PHASE_ORDER, P265R_EARLY_RESIDUAL,
+        (int)ctx->params.bit_depth_luma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], 0ll,
+        "lds tile", 0, ctx->last_expand_ms,
         ctx->describe.c_str());
     if (n < 0) return P265R_EINVAL;
     if (size > 0) {

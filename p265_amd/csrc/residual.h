@@ -19,13 +19,8 @@
 
 namespace p265r {
 
-#ifndef P265R_RES_NT
-#define P265R_RES_NT 0   // A/B: residual stores non-temporal (the row kernel reads them a phase later)
-#endif
-typedef unsigned int res_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void res_store16(int16_t* p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    if constexpr (P265R_RES_NT) __builtin_nontemporal_store(res_u4{a, b, c, d}, reinterpret_cast<res_u4*>(p));
-    else *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
+    *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 }
 
 __device__ __forceinline__ int clamp16(long long v) {
@@ -111,7 +106,6 @@ __global__ __launch_bounds__(256) void residual4_kernel(const int16_t* __restric
                                                         int16_t* __restrict__ res,
                                                         const ResJob* __restrict__ jobs, int n_jobs,
                                                         int bit_depth, uint32_t slab, const uint8_t* __restrict__ sf) {
-    P265R_BW_PRIO_SET();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_jobs) return;
     const ResJob jb = jobs[i];
@@ -172,38 +166,13 @@ __global__ __launch_bounds__(256) void residual4_kernel(const int16_t* __restric
 // for n < N/2), odd rows antisymmetric, so x[n] = E[n] + O[n] and x[N-1-n] = E[n] - O[n] with E the
 // N/2-point transform of the even coefficients.  Same integer sum as the matrix product (exact),
 // about N^2/3 instead of N^2 multiply-adds.
-// ---------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void inv_dct_eo(const int (&c)[N], int (&x)[N]) {
-    constexpr int H = N / 2;
-    constexpr int S = 32 / N;
-    int ce[H], ev[H];
-#pragma unroll
-    for (int k = 0; k < H; ++k) ce[k] = c[2 * k];
-    if constexpr (H == 2) {
-        ev[0] = kDCT32[0][0] * ce[0] + kDCT32[16][0] * ce[1];
-        ev[1] = kDCT32[0][1] * ce[0] + kDCT32[16][1] * ce[1];
-    } else {
-        inv_dct_eo<H>(ce, ev);
-    }
-#pragma unroll
-    for (int n = 0; n < H; ++n) {
-        int od = 0;
-#pragma unroll
-        for (int j = 0; j < H; ++j) od += kDCT32[(2 * j + 1) * S][n] * c[2 * j + 1];
-        x[n] = ev[n] + od;
-        x[N - 1 - n] = ev[n] - od;
-    }
-}
-
-// The same butterfly with the odd parts as packed 16-bit dot products: every input of either stage is an
+//
+// The odd parts are packed 16-bit dot products: every input of either stage is an
 // int16 (dequantised coefficients and the stage-1 output are clipped to 16 bits), so two odd coefficients
 // pack into one register and one v_dot2c_i32_i16 with a literal pair of matrix entries adds two products
-// into the 32-bit sum (exact: |sum| < 2^15 * 90 * 32 < 2^31).  About half the multiply-add instructions of
-// inv_dct_eo, the same integer result.
-#ifndef P265R_RES_DOT2
-#define P265R_RES_DOT2 1
-#endif
+// into the 32-bit sum (exact: |sum| < 2^15 * 90 * 32 < 2^31): about half the multiply-add instructions of
+// plain products, the same integer result.
+// ---------------------------------------------------------------------------
 typedef short res_v2s __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack16(int lo, int hi) {          // (int16) lo | (int16) hi << 16
     return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
@@ -263,7 +232,6 @@ __global__ __launch_bounds__(256) void residualN_kernel(const int16_t* __restric
                                                        const ResJob* __restrict__ jobs, int n_jobs,
                                                        int bit_depth_luma, int bit_depth_chroma, uint32_t slab,
                                                        const uint8_t* __restrict__ sf) {
-    P265R_BW_PRIO_SET();
     constexpr int N = 1 << LOG2;
     constexpr int TPB = 256 / N;                 // TBs per block
     constexpr int S = N + 2;                     // padded LDS row (odd dword stride)
@@ -311,37 +279,18 @@ __global__ __launch_bounds__(256) void residualN_kernel(const int16_t* __restric
         int col[N], e[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) col[k] = t[k * S + lane];
-#ifdef P265R_RES_NOMATH   // timing experiment only (wrong results): the transform's arithmetic removed
+        inv_dct_d2<N>(col, e, 1);                                    // (+64 folded in)
 #pragma unroll
-        for (int k = 0; k < N; ++k) e[k] = col[k] << 7;
-#else
-        if constexpr (P265R_RES_DOT2) inv_dct_d2<N>(col, e, 1); else inv_dct_eo<N>(col, e);   // (+64 folded in)
-#endif
-#pragma unroll
-        for (int y = 0; y < N; ++y) t[y * S + lane] = (int16_t)clamp16i((e[y] + (P265R_RES_DOT2 ? 0 : 64)) >> 7);
+        for (int y = 0; y < N; ++y) t[y * S + lane] = (int16_t)clamp16i(e[y] >> 7);
     }
     __syncthreads();
     if (active) {
         int row[N], xr[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) row[k] = t[lane * S + k];
-#ifdef P265R_RES_NOMATH
-#pragma unroll
-        for (int k = 0; k < N; ++k) xr[k] = row[k];
-#else
         // (8-bit video: bdShift 12, its rounding 2048 = 64 * 32 folded into the butterfly)
-        if constexpr (P265R_RES_DOT2) inv_dct_d2<N>(row, xr, 1 << (19 - bit_depth - 6)); else inv_dct_eo<N>(row, xr);
-#endif
+        inv_dct_d2<N>(row, xr, 1 << (19 - bit_depth - 6));
         const int bd2 = 20 - bit_depth;
-        const int rnd2 = 1 << (bd2 - 1);
-#ifdef P265R_RES_PADV     // timing experiment only: P265R_RES_PADV dependent VALU per thread
-        {
-            uint32_t z = (uint32_t)lane;
-#pragma unroll
-            for (int q = 0; q < P265R_RES_PADV; ++q) asm volatile("v_add_u32 %0, 1, %0" : "+v"(z));
-            asm volatile("" :: "v"(z));
-        }
-#endif
 #pragma unroll
         for (int v = 0; v < N / 8; ++v) {
             uint32_t o[4];
@@ -351,7 +300,7 @@ __global__ __launch_bounds__(256) void residualN_kernel(const int16_t* __restric
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int x = v * 8 + h * 2 + q;
-                    r2[q] = clamp16i((xr[x] + (P265R_RES_DOT2 ? 0 : rnd2)) >> bd2);
+                    r2[q] = clamp16i(xr[x] >> bd2);
                 }
                 o[h] = (uint32_t)(uint16_t)r2[0] | ((uint32_t)(uint16_t)r2[1] << 16);
             }

@@ -108,7 +108,7 @@ __device__ __forceinline__ StripPos strip_pos(const DevPic* __restrict__ pics, c
     else { p.c = 1 + (u - nsl) / nsc; p.sx = (u - nsl) % nsc; }
     const int c = p.c;
     p.g = gb;
-    if (P265R_RAGGED && gb.ragged) {                              // this picture's size and CTU raster
+    if (gb.ragged) {                              // this picture's size and CTU raster
         p.g = pic_geo(gb, (uint32_t)__builtin_amdgcn_readfirstlane((int)pics[p.pic].wh));
         p.outside = p.outside || p.cy >= p.g.hc || p.sx * strip >= (c ? p.g.cw : p.g.w);
     }

@@ -27,7 +27,6 @@ __device__ __forceinline__ int off_e(uint32_t o, int e) { return (int)(int8_t)(o
 __global__ __launch_bounds__(256) void sao16_strip_kernel(const DevPic* __restrict__ pics, Geo gb, BatchView v, int n_pics) {
     typedef unsigned int u4v __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(1))) uint16_t gu16;
-    P265R_BW_PRIO_SET();
     const StripPos p = strip_pos<8>(pics, gb, n_pics, gb.ctb_log2);
     if (p.outside) return;                                        // whole wave (no barriers below)
     const Geo& g = p.g;

@@ -18,10 +18,7 @@
 
 namespace p265r {
 
-#ifndef P265R_SAO_CHUNK
-#define P265R_SAO_CHUNK 8
-#endif
-constexpr int kSaoRowsChunk = P265R_SAO_CHUNK;   // output rows per load batch
+constexpr int kSaoRowsChunk = 8;   // output rows per load batch
 
 // grid: 4 waves per block, one wave per (picture, CTB row, component, 248-sample strip), XCD-aware
 // order (sao.h strip_pos)

@@ -46,30 +46,19 @@ __device__ __forceinline__ void expand_mask(uint32_t m16, uint32_t* d) {
     }
 }
 
-#ifndef P265R_SAO_WPE
-#define P265R_SAO_WPE 6
-#endif
-
-#ifndef P265R_SAO_NT
-#define P265R_SAO_NT 0                     // A/B: 1 non-temporal output stores, 2 non-temporal loads too
-#endif
-
-#ifndef P265R_SAO16_CHUNK
-#define P265R_SAO16_CHUNK 2
-#endif
+constexpr int kSao16Wpe = 6;               // the kernel's waves-per-SIMD attribute
 // rows per load batch: 2 (80 VGPRs, 6 waves per SIMD) rather than 4 (100 VGPRs): 0.74 -> 0.77 ms
 // alone, but two SAO waves per SIMD fit beside the W = 8 row kernel of another lane: pipelined
 // 46.9-47.1 -> 47.0-48.0 M CTU/s (3 interleaved reps, round 3)
-constexpr int kSao16Chunk = P265R_SAO16_CHUNK;
+constexpr int kSao16Chunk = 2;
 
 // grid: 4 waves per block, one wave per (picture, CTB row, component, 992-sample strip), XCD-aware
 // order (sao.h strip_pos)
 template <int L>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(P265R_SAO_WPE))) void sao_strip16_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSao16Wpe))) void sao_strip16_kernel(
         const DevPic* __restrict__ pics, Geo gb, BatchView v, int n_pics) {
     typedef unsigned int u4v __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(1))) uint8_t gu8;
-    P265R_BW_PRIO_SET();
     const StripPos p = strip_pos<16>(pics, gb, n_pics, L);
     if (p.outside) return;                                        // whole wave (no barriers below)
     const Geo& g = p.g;
@@ -82,10 +71,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(P265R_SAO_W
     const gu8* src = (const gu8*)(v.rec0 + pofs);
     gu8* dst = (gu8*)(v.out0 + pofs);
     auto row_ld = [&](int y) {
-        const __attribute__((address_space(1))) u4v* p =
-            (const __attribute__((address_space(1))) u4v*)(src + __umul24((uint32_t)min(max(y, 0), H - 1), (uint32_t)st) + Xc);
-        if constexpr (P265R_SAO_NT >= 2) return __builtin_nontemporal_load(p);
-        else return *p;
+        return *(const __attribute__((address_space(1))) u4v*)(src + __umul24((uint32_t)min(max(y, 0), H - 1), (uint32_t)st) + Xc);
     };
     // ---- first: the rows of the first chunk (position only) ----------------------------------
     constexpr int K = kSao16Chunk;
@@ -192,8 +178,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(P265R_SAO_W
                 }
                 if (act && y < ye) {
                     __attribute__((address_space(1))) u4v* q = (__attribute__((address_space(1))) u4v*)(dst + __umul24((uint32_t)y, (uint32_t)st) + Xc);
-                    if constexpr (P265R_SAO_NT >= 1) __builtin_nontemporal_store(u4v{out[0], out[1], out[2], out[3]}, q);
-                    else *q = u4v{out[0], out[1], out[2], out[3]};
+                    *q = u4v{out[0], out[1], out[2], out[3]};
                 }
             }
             rowv[0] = rowv[K];

@@ -87,7 +87,7 @@ int validate_picture(const p265r_params& p, const Geo& geo, const p265r_picture&
 }
 
 int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool split, int num_cus, const p265r_picture* pics,
-                const p265r_sparse_coef* sp, int n_pics, UploadPlan* plan, std::chrono::steady_clock::time_point* counted) {
+                const p265r_sparse_coef* sp, int n_pics, UploadPlan* plan) {
     if (!pics || n_pics <= 0 || !plan) return P265R_EINVAL;
     if (n_pics > 65535) return P265R_ERANGE;                     // pictures index a grid dimension
     for (int i = 0; i < n_pics; ++i)
@@ -149,7 +149,6 @@ int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool sp
     });
     for (int i = 0; i < n_pics; ++i)
         if (crc[i]) return crc[i];
-    if (counted) *counted = std::chrono::steady_clock::now();
     // per-picture start offsets (row n_pics: the totals)
     u.pool_at.resize(n_pics + 1);
     u.job_at.resize(n_pics + 1);

@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
-#include <chrono>
 #include <cstddef>
 #include <thread>
 #include <vector>
@@ -110,10 +109,9 @@ struct UploadPlan {
 // Validates every record (on up to 16 host threads; the first failing picture's code is returned), counts the
 // coded TBs per class and lays the upload out.  sp null: dense coefficients; else sp[i] holds the entries of
 // pics[i]'s transformed TBs.  n_ctus: CTUs of a picture of the context size; xg, split, num_cus: whether the
-// batch gets the cross-group row kernel's ranges (xg_ok).  P265R_OK, P265R_EINVAL or P265R_ERANGE.  counted
-// (optional; the experiments build's stage timer): when the validate-and-count pass ended.
+// batch gets the cross-group row kernel's ranges (xg_ok).  P265R_OK, P265R_EINVAL or P265R_ERANGE.
 int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool split, int num_cus, const p265r_picture* pics,
-                const p265r_sparse_coef* sp, int n_pics, UploadPlan* plan, std::chrono::steady_clock::time_point* counted = nullptr);
+                const p265r_sparse_coef* sp, int n_pics, UploadPlan* plan);
 
 // Picture i's share of the staging buffer (stage_need bytes at `stage`) and its DevPic, whose pointers are
 // offsets from dbase, the device image's address.  Pictures are independent: callable from parallel_for.

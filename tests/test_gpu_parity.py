@@ -50,8 +50,7 @@ def _check(recon_mod, params, pics, label=""):
 # smaller ones each chain on P265R_XG workgroups of 4 waves with progress and lines in global memory
 # (default 4, "rows_auto"; 2 and 8; 0: the one-workgroup-per-chain W = 16 layout); P265R_TR_CHECK=1 poisons
 # the top-right part of a CTU's row-above copy until the top-right wait, so a job the prep kernel placed
-# before that wait but which reads the top-right CTU fails parity deterministically (not by timing).  (W = 4 / 6 / 10 / 16
-# and the unconstrained W = 8 build exist only in the experiments build, p265r.hip P265R_EXPERIMENTS.)
+# before that wait but which reads the top-right CTU fails parity deterministically (not by timing).
 ROW_VARIANTS = {"rows": {"P265R_ROW_WAVES": "8"}, "rows_auto": {},
                 "rows_nosplit": {"P265R_SPLIT": "0"},
                 "rows_w16": {"P265R_XG": "0"}, "rows_xg2": {"P265R_XG": "2", "P265R_TR_CHECK": "1"},

@@ -8,8 +8,6 @@ sparsified beforehand) alternately -- one warm-up each, then R timed repeats -- 
 upload_bytes, upload wall time (median, min, max), the expand kernels' time (HIP events), the host
 sparsify time (p265r_sparsify, one thread, separately) and coef_nonzero_frac.  The sparse batch's device
 digests (output and reconstruction) are checked against the dense batch's before anything is printed.
-P265R_LIB selects another build of the library (make variant: -DP265R_EXPAND_SCATTER=1,
--DP265R_EXPAND_STREAM=1) for the A/B of the expand shapes.
 """
 import argparse
 import json
@@ -67,7 +65,6 @@ def main(argv=None):
                     if kind == "sparse":
                         expand.append(float(ctx.describe()["last_sparse_expand_ms"]))
                 b.free()
-        desc = ctx.describe()
     for k in (0, 1):
         if not np.array_equal(digests["dense"][k], digests["sparse"][k]):
             raise SystemExit("sparse upload: device digests differ from the dense upload's")
@@ -81,7 +78,6 @@ def main(argv=None):
            "upload_bytes": nbytes, "bytes_ratio": round(nbytes["sparse"] / nbytes["dense"], 4),
            "upload_ms": {k: stats(v) for k, v in wall.items()},
            "expand_kernels_ms": stats(expand),
-           "expand": desc["sparse_expand"], "expand_stream": desc["sparse_expand_stream"],
            "sparsify_ms_per_picture": round(statistics.median(t_sp) * 1e3, 3),
            "sparsify_ms_batch_one_thread": round(statistics.median(t_sp) * 1e3 * a.pictures, 1),
            "digests_equal": True}
