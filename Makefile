@@ -46,7 +46,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -75,6 +75,16 @@ export-check: tools/export_check.cpp p265_amd/csrc/export_host.cpp p265_amd/csrc
 		-o tools/export_check tools/export_check.cpp p265_amd/csrc/export_host.cpp
 	./tools/export_check
 .PHONY: export-check
+
+# host sanitizer check of the monochrome (chroma_format_idc 0) forms: the upload's planner, packer and validation
+# for pictures without chroma (malformed ones included) and the one-plane export layouts: a stand-alone CPU program,
+# not part of `all`
+mono-check: tools/mono_check.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/sparse_host.cpp p265_amd/csrc/export_host.cpp \
+            p265_amd/csrc/upload_host.h p265_amd/csrc/sparse_host.h p265_amd/csrc/export_host.h p265_amd/csrc/batch_types.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -pthread -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o tools/mono_check tools/mono_check.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/sparse_host.cpp p265_amd/csrc/export_host.cpp
+	./tools/mono_check
+.PHONY: mono-check
 
 # host sanitizer check of the picture hash arithmetic (pichash_math.h through p265r_plane_hash_host: RFC 1321's
 # vectors, the CRC and checksum split forms against restatements of D.3.19, rejection codes): a stand-alone CPU

@@ -19,7 +19,12 @@
  * p265r_tb per transform block (grouped by CTU, decode order inside a CTU), dense
  * int16 coefficients in decode order, and the optional no-filter map.
  *
- * Scope: 4:2:0, 8..14-bit syntax (the back-end reconstructs 8-bit), I slices only
+ * Scope: 4:2:0 and monochrome 4:0:0 (ChromaArrayType 0 syntax of the 10/2014 and later text: one component in
+ * sao(), no intra_chroma_pred_mode, no cbf_cb / cbf_cr (cbfChroma = 0 in the cu_qp_delta condition), no chroma TB
+ * record or PCM sample; the parameters handed on carry chroma_format_idc 0, bit_depth_chroma = bit_depth_luma and
+ * zero chroma QP offsets -- the SPS / PPS / slice values are parsed and ignored -- the conformance window is in
+ * luma samples, the picture hash has one component); 4:2:2, 4:4:4 and separate_colour_plane_flag = 1 ->
+ * P265FE_EUNSUPPORTED.  8..14-bit syntax (the back-end reconstructs 8..12), I slices only
  * (P/B slices -> P265FE_EUNSUPPORTED), tiles, WPP (entropy_coding_sync), multiple
  * and dependent slice segments, PCM, cu_transquant_bypass, transform_skip, sign data
  * hiding, cu_qp_delta, deblocking/SAO syntax, decoded-picture-hash SEI.  Scaling lists

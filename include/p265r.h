@@ -18,6 +18,24 @@
  * reconstruction + SAO and writes the decoded planes.  See INTEGRATION.md for the
  * ctypes binding the reference would add.
  *
+ * Chroma formats: 4:2:0 (chroma_format_idc 1) and monochrome 4:0:0 (chroma_format_idc 0), BitDepth 8..12.
+ * A monochrome context has no chroma anywhere -- every array keeps its shape, the chroma entries are not used:
+ *   p265r_params    bit_depth_chroma, pps_cb / cr_qp_offset and the chroma entries of a scaling table are ignored
+ *   records         a TB with c_idx != 0 or a non-zero sao_type[1..2] is P265R_EINVAL at upload, before any launch
+ *   p265r_picture   out[1..2] and recon[1..2] are never read or written (P265R_PIC_RECON_INPUT takes recon[0] alone)
+ *   p265r_batch_digest*     out[3 i + 1] = out[3 i + 2] = 0;  p265r_batch_hash_read: bytes 16..47 of a picture are 0
+ *   p265r_batch_job_count   chroma = 0
+ *   p265r_batch_export      P265R_FMT_PLANAR is the Y plane alone (the layout sets plane_off[1..2] = pitch[1..2] = 0);
+ *                           P265R_FMT_SEMIPLANAR is Y plus a CbCr plane whose every element is 1 << (B - 1) (shifted
+ *                           for MSB16): grey NV12 / P010; the RGB formats give R = G = B = clip((cy (Y - yoff) + 8192)
+ *                           >> 14), the formula below at cb = cr = 0 (matrix and upsample are validated, otherwise
+ *                           unused).  Crops may be odd for planar and RGB (SubWidthC = SubHeightC = 1); semi-planar
+ *                           keeps the even rule of its 2 x 2-subsampled plane.
+ *   p265r_describe  "chroma_format_idc", and "last_launch_layout" (the intra phase of the last run: "whole" |
+ *                   "split" | "xg" | "luma" = the row kernel's luma-rows-only layout, which every monochrome
+ *                   batch takes | "steps" | "none") with "last_launch_row_waves"
+ * chroma_format_idc 2 and 3 are P265R_EINVAL from p265r_create.
+ *
  * Conventions: every function returns int (0 = P265R_OK, < 0 = error code, see
  * p265r_strerror); no exception or C++ type crosses this boundary.  All host
  * buffers are owned by the caller.  A context is bound to one device and is not
@@ -72,9 +90,9 @@ typedef struct p265r_params {
     uint32_t version;                 /* = P265R_ABI_VERSION                      */
     uint16_t pic_width;               /* pic_width_in_luma_samples                */
     uint16_t pic_height;              /* pic_height_in_luma_samples               */
-    uint8_t  chroma_format_idc;       /* 1 (4:2:0) only                           */
+    uint8_t  chroma_format_idc;       /* 1 (4:2:0) or 0 (4:0:0, monochrome)       */
     uint8_t  bit_depth_luma;          /* BitDepthY: 8, or 9..12 (uint16_t planes)   */
-    uint8_t  bit_depth_chroma;        /* BitDepthC: equal to bit_depth_luma        */
+    uint8_t  bit_depth_chroma;        /* BitDepthC: equal to bit_depth_luma (monochrome: ignored) */
     uint8_t  ctb_log2_size;           /* CtbLog2SizeY, 4..6                       */
     uint8_t  min_tb_log2_size;        /* MinTbLog2SizeY, 2..5                     */
     uint8_t  max_tb_log2_size;        /* MaxTbLog2SizeY, <= 5                     */

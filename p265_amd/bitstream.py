@@ -219,7 +219,7 @@ def _collect(get, n, owner, validate, base=0):
         if validate:
             R.validate(params, pic)
         hl = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}.get(int(info.hash_type))
-        hv = [bytes(info.hash[c][:hl]) for c in range(3)] if hl else None
+        hv = [bytes(info.hash[c][:hl]) for c in range(R.n_planes(params))] if hl else None   # (4:0:0: one component)
         out.append(DecodedPicture(params=params, picture=pic, poc=int(info.poc),
                                   output_rank=int(info.output_rank),
                                   crop=(info.crop_left, info.crop_right, info.crop_top, info.crop_bottom),

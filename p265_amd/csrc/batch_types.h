@@ -44,7 +44,7 @@ struct BatchView {
 
 struct Geo {                    // batch-uniform geometry
     int w, h;                   // luma size
-    int cw, ch;                 // chroma size
+    int cw, ch;                 // chroma size (4:2:0: w / 2, h / 2; monochrome: 0, 0)
     int stride[3];
     int ctb_log2, wc, hc;
     int bd[3];
@@ -71,6 +71,9 @@ struct Geo {                    // batch-uniform geometry
                                 // checks `br` against the TBs' extents (error word bit 1)
     int pel16;                  // samples are 16-bit (BitDepth 9..12): planes of stride[] samples of 2
                                 // bytes, the per-diagonal intra kernel and loopfilter16.h (else uint8_t)
+    int mono;                   // chroma_format_idc 0: cw = ch = 0, no chroma plane, record, job or row exists
+                                // (DevPic::rec[1..2] / out[1..2] are null); every kernel's chroma work is behind
+                                // a bounds test against cw / ch or is not launched
 };
 
 struct ResJob {          // 8 bytes, one per coded TB, in pool order within its class

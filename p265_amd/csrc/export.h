@@ -306,4 +306,87 @@ __global__ __launch_bounds__(256) void export_rgb_kernel(const DevPic* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Monochrome sources (Geo::mono, 4:0:0): the same groups, heads and stores; no chroma plane exists or is read.
+// ---------------------------------------------------------------------------------------
+// YUV.  Row units of a picture: H luma rows (planar: one plane, that is all), then -- semi-planar -- H / 2 CbCr rows
+// of W elements, every one `grey` = (1 << (B - 1)) << shift: grey NV12 / P010 for consumers that take nothing else.
+template <typename S, bool SEMI>
+__global__ __launch_bounds__(256) void export_mono_yuv_kernel(const DevPic* __restrict__ pics, Geo g, ExportArgs a, int grey) {
+    constexpr int E = 16 / (int)sizeof(S);
+    const int slot = blockIdx.z;
+    const ExportPic e = export_pic(pics, a, slot);
+    int r = blockIdx.y * kExportRows + (int)(threadIdx.x >> 6);                 // (wave-uniform)
+    if (r >= (SEMI ? e.H + e.H / 2 : e.H)) return;
+    const int k = r >= e.H ? 1 : 0;
+    if (k) r -= e.H;
+    const int gi = blockIdx.x * kExportLanes + (int)(threadIdx.x & 63);
+    uint8_t* base = a.dst + (uint64_t)slot * a.frame_bytes + a.plane_off[k];
+    uint8_t* drow = base + (uint64_t)r * a.pitch[k];
+    const int units = e.W;                                                      // luma samples / W / 2 CbCr pairs
+    const int h = export_head<(int)sizeof(S)>((uint64_t)(uintptr_t)base);
+    const bool vec = h >= 0 && a.pitch[k] % 16 == 0;
+    const int u0 = (vec && h > 0 ? h - E : 0) + gi * E;
+    if (u0 >= units) return;
+    const int lo = max(0, -u0), hi = min(E, units - u0);
+    S v[E];
+    if (k) {
+#pragma unroll
+        for (int i = 0; i < E; ++i) v[i] = (S)grey;
+    } else {
+        const size_t so = (size_t)(a.crop_t + r) * g.stride[0] + a.crop_l;
+        export_load_row<S, E>(reinterpret_cast<const S*>(e.P->out[0]) + so, u0, units, lo == 0 && hi == E, v);
+        if (sizeof(S) == 2) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) v[i] = (S)(v[i] << a.shift);
+        }
+    }
+    export_store<S, E>(reinterpret_cast<S*>(drow) + u0, v, lo, hi, vec);
+}
+
+// RGB: R = G = B = Clip((cy (Y - yoff) + 8192) >> 14), the formula of export_rgb_row at Cb = Cr = 1 << (B - 1).
+// grid (ceil(groups of the widest row / 64), ceil(rows / 4), slots): one window row per wave.
+template <typename S, typename D, bool PACKED>
+__global__ __launch_bounds__(256) void export_mono_rgb_kernel(const DevPic* __restrict__ pics, Geo g, ExportArgs a) {
+    constexpr int G = sizeof(D) == 1 ? 16 : 8;
+    constexpr int UB = (PACKED ? 3 : 1) * (int)sizeof(D);
+    constexpr int NP = PACKED ? 1 : 3;
+    const int slot = blockIdx.z;
+    const ExportPic e = export_pic(pics, a, slot);
+    const int r = blockIdx.y * kExportRows + (int)(threadIdx.x >> 6);           // (wave-uniform)
+    if (r >= e.H) return;
+    uint8_t* base[NP];
+    bool vec[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) base[k] = a.dst + (uint64_t)slot * a.frame_bytes + a.plane_off[k];
+    int h = export_head<UB>((uint64_t)(uintptr_t)base[0]);
+    if (h < 0 || a.pitch[0] % 16 != 0) h = 0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+        vec[k] = a.pitch[k] % 16 == 0 && (((uint64_t)(uintptr_t)base[k] + (uint64_t)(h * UB)) & 15) == 0;
+    const int gi = blockIdx.x * kExportLanes + (int)(threadIdx.x & 63);
+    const int x0 = (h > 0 ? h - G : 0) + gi * G;                                // in the window
+    if (x0 >= e.W) return;
+    const int lo = max(0, -x0), hi = min(G, e.W - x0);
+    const S* Y = reinterpret_cast<const S*>(e.P->out[0]) + (size_t)(a.crop_t + r) * g.stride[0] + a.crop_l;
+    S la[G];
+    export_load_row<S, G>(Y, x0, e.W, lo == 0 && hi == G, la);
+    const int cy = a.coef[0], yoff = a.coef[5], top = (1 << a.coef[7]) - 1;
+    D o[3 * G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const D d = export_sample<D>(min(max((cy * ((int)la[i] - yoff) + 8192) >> 14, 0), top), a.fscale);
+        o[PACKED ? 3 * i : i] = d;
+        o[PACKED ? 3 * i + 1 : G + i] = d;
+        o[PACKED ? 3 * i + 2 : 2 * G + i] = d;
+    }
+    if (PACKED) {
+        export_store<D, 3 * G>(reinterpret_cast<D*>(base[0] + (uint64_t)r * a.pitch[0]) + 3 * x0, o, 3 * lo, 3 * hi, vec[0]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NP; ++k)
+            export_store<D, G>(reinterpret_cast<D*>(base[k] + (uint64_t)r * a.pitch[k]) + x0, o + k * G, lo, hi, vec[k]);
+    }
+}
+
 }  // namespace p265r

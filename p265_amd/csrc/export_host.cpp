@@ -6,7 +6,7 @@
 
 namespace p265r {
 
-int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s) {
+int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s, bool mono) {
     if (bit_depth < 8 || bit_depth > 12) return P265R_EINVAL;
     if (d.format > P265R_FMT_RGB_PACKED || d.sample > P265R_SMP_F32) return P265R_EINVAL;
     const bool rgb = d.format >= P265R_FMT_RGB_PLANAR;
@@ -17,7 +17,10 @@ int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s)
         if (d.sample != P265R_SMP_NATIVE && d.sample != P265R_SMP_MSB16) return P265R_EINVAL;
         if (d.sample == P265R_SMP_MSB16 && bit_depth == 8) return P265R_EINVAL;
     }
-    if ((d.crop_left | d.crop_right | d.crop_top | d.crop_bottom) & 1) return P265R_EINVAL;
+    // crops in whole chroma samples: 4:2:0 sources, and the 2 x 2-subsampled CbCr plane semi-planar always has
+    // (monochrome: SubWidthC = SubHeightC = 1, any crop, for the formats without one)
+    if (!(mono && d.format != P265R_FMT_SEMIPLANAR) && ((d.crop_left | d.crop_right | d.crop_top | d.crop_bottom) & 1))
+        return P265R_EINVAL;
     switch (d.sample) {
         case P265R_SMP_NATIVE: s->es = bit_depth > 8 ? 2 : 1; break;
         case P265R_SMP_U8: s->es = 1; break;
@@ -25,7 +28,9 @@ int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s)
         default: s->es = 2; break;                       // MSB16, F16
     }
     s->rgb = rgb ? 1 : 0;
+    s->mono = mono ? 1 : 0;
     s->n_planes = d.format == P265R_FMT_SEMIPLANAR ? 2 : (d.format == P265R_FMT_RGB_PACKED ? 1 : 3);
+    if (mono && d.format == P265R_FMT_PLANAR) s->n_planes = 1;
     return P265R_OK;
 }
 
@@ -33,6 +38,11 @@ int export_planes(const p265r_export_desc& d, const ExportShape& s, int pw, int 
     const int w = pw - d.crop_left - d.crop_right, h = ph - d.crop_top - d.crop_bottom;
     if (pw <= 0 || ph <= 0 || (pw & 1) || (ph & 1) || w <= 0 || h <= 0) return P265R_EINVAL;
     const uint64_t luma = (uint64_t)w * s.es;
+    if (s.mono && d.format == P265R_FMT_PLANAR) {            // the luma plane alone
+        pl[0] = {luma, h};
+        pl[1] = pl[2] = {0, 0};
+        return P265R_OK;
+    }
     switch (d.format) {
         case P265R_FMT_PLANAR: pl[0] = {luma, h}; pl[1] = pl[2] = {luma / 2, h / 2}; break;
         case P265R_FMT_SEMIPLANAR: pl[0] = {luma, h}; pl[1] = {luma, h / 2}; pl[2] = {0, 0}; break;
@@ -91,12 +101,13 @@ extern "C" {
 
 int p265r_export_layout(const p265r_params* params, int pic_width, int pic_height, p265r_export_desc* desc,
                         uint32_t pitch_align) {
-    if (!params || !desc || params->version != P265R_ABI_VERSION || params->bit_depth_chroma != params->bit_depth_luma)
-        return P265R_EINVAL;
+    if (!params || !desc || params->version != P265R_ABI_VERSION) return P265R_EINVAL;
+    const bool mono = params->chroma_format_idc == 0;        // (bit_depth_chroma means nothing then)
+    if (!mono && params->bit_depth_chroma != params->bit_depth_luma) return P265R_EINVAL;
     const int pw = pic_width ? pic_width : params->pic_width, ph = pic_height ? pic_height : params->pic_height;
     if (pw <= 0 || ph <= 0 || pw > 0xffff || ph > 0xffff || pitch_align > (1u << 20)) return P265R_EINVAL;
     ExportShape s;
-    if (const int rc = export_check_desc(*desc, params->bit_depth_luma, &s)) return rc;
+    if (const int rc = export_check_desc(*desc, params->bit_depth_luma, &s, mono)) return rc;
     ExportPlane pl[3];
     if (const int rc = export_planes(*desc, s, pw, ph, pl)) return rc;
     const uint64_t a = pitch_align > 1 ? pitch_align : 1;

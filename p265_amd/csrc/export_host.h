@@ -11,6 +11,8 @@ struct ExportShape {
     int es;             // bytes of one destination element
     int n_planes;       // destination planes: 3 planar / RGB planar, 2 semi-planar, 1 RGB packed
     int rgb;            // an RGB format
+    int mono;           // the source is monochrome (4:0:0): planar has one plane, odd crops are legal except for
+                        // semi-planar (whose CbCr plane is written as mid-grey)
 };
 
 struct ExportPlane {    // one destination plane of one cropped picture
@@ -19,7 +21,8 @@ struct ExportPlane {    // one destination plane of one cropped picture
 };
 
 // enums, sample type against format and bit depth, crop parity (P265R_EINVAL)
-int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s);
+// (mono: the source pictures are 4:0:0)
+int export_check_desc(const p265r_export_desc& d, int bit_depth, ExportShape* s, bool mono = false);
 // the planes of a pw x ph picture under d's crop; P265R_EINVAL when the crop leaves no sample
 int export_planes(const p265r_export_desc& d, const ExportShape& s, int pw, int ph, ExportPlane pl[3]);
 // plane_off / pitch / frame_bytes against a pw x ph picture: pitches, element alignment, overlap, slot

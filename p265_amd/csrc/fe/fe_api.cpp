@@ -346,7 +346,9 @@ void fill_info(const PictureJob& j, const PictureRecords& r, p265fe_picture_info
     pr.pic_height = (uint16_t)s.height;
     pr.chroma_format_idc = (uint8_t)s.chroma_format_idc;
     pr.bit_depth_luma = (uint8_t)s.bit_depth_y;
-    pr.bit_depth_chroma = (uint8_t)s.bit_depth_c;
+    // (monochrome: the SPS's bit_depth_chroma and the PPS's chroma QP offsets mean nothing to the back-end)
+    const bool mono = s.chroma_format_idc == 0;
+    pr.bit_depth_chroma = (uint8_t)(mono ? s.bit_depth_y : s.bit_depth_c);
     pr.ctb_log2_size = (uint8_t)s.log2_ctb;
     pr.min_tb_log2_size = (uint8_t)s.log2_min_tb;
     pr.max_tb_log2_size = (uint8_t)s.log2_max_tb;
@@ -355,8 +357,8 @@ void fill_info(const PictureJob& j, const PictureRecords& r, p265fe_picture_info
     pr.sample_adaptive_offset = (uint8_t)s.sao;
     pr.loop_filter_across_tiles = (uint8_t)p.loop_filter_across_tiles;
     pr.scaling_list_enabled = (uint8_t)s.scaling_list_enabled;
-    pr.pps_cb_qp_offset = (int8_t)p.cb_qp_offset;
-    pr.pps_cr_qp_offset = (int8_t)p.cr_qp_offset;
+    pr.pps_cb_qp_offset = (int8_t)(mono ? 0 : p.cb_qp_offset);
+    pr.pps_cr_qp_offset = (int8_t)(mono ? 0 : p.cr_qp_offset);
     out->ctus = r.ctus.data();
     out->n_ctus = (uint32_t)r.ctus.size();
     out->tbs = r.tbs.data();

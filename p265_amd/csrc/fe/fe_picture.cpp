@@ -204,6 +204,7 @@ public:
         for (auto& c : out_.ctus) c.flags = P265R_CTU_LF_ACROSS_SLICES;
         qp_bd_y_ = 6 * (sps_.bit_depth_y - 8);
         qp_bd_c_ = 6 * (sps_.bit_depth_c - 8);
+        mono_ = sps_.chroma_format_idc == 0;
     }
 
     void decode_segment(const SliceRef& s) {
@@ -379,6 +380,7 @@ private:
             c.sao_type[ci] = 0;
             c.sao_class[ci] = 0;
             std::memset(c.sao_offset[ci], 0, 4);
+            if (mono_ && ci > 0) continue;          // ChromaArrayType 0: one component in sao()
             if (!((h.sao_luma && ci == 0) || (h.sao_chroma && ci > 0))) continue;
             int type;
             if (ci == 2) {
@@ -559,8 +561,8 @@ private:
                 set_ipm(xp, yp, pb, modes_y_[i]);
             }
             // intra_chroma_pred_mode (9.3.3.8 binarization; 8.4.3 derivation, Table 8-2/8-3)
-            int icpm = 4;
-            if (dec(C_CHROMA_MODE)) icpm = (int)cabac_.bypass_bits(2);
+            int icpm = 4;                         // (ChromaArrayType 0: no intra_chroma_pred_mode; mode_c unused)
+            if (!mono_ && dec(C_CHROMA_MODE)) icpm = (int)cabac_.bypass_bits(2);
             if (icpm == 4) {
                 mode_c = modes_y_[0];
             } else {
@@ -592,7 +594,7 @@ private:
     void pcm_sample(int x0, int y0, int log2) {
         size_t byte = cabac_.aligned_byte_after_terminate();   // pcm_alignment_zero_bit(s) skipped
         BitReader br(rbsp_, rbsp_size_, byte * 8);
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < (mono_ ? 1 : 3); ++c) {      // ChromaArrayType 0: pcm_sample_luma alone
             int lg = c ? log2 - 1 : log2;
             int n = 1 << lg;
             int pbd = c ? sps_.pcm_bit_depth_c : sps_.pcm_bit_depth_y;
@@ -623,7 +625,7 @@ private:
         else
             split = (log2 > sps_.log2_max_tb || (part_nxn_ && depth == 0)) ? 1 : 0;
         int cbf_cb = 0, cbf_cr = 0;
-        if (log2 > 2) {
+        if (log2 > 2 && !mono_) {                  // ChromaArrayType 0: no cbf_cb / cbf_cr, both 0
             if (depth == 0 || parent_cb) cbf_cb = dec(C_CBF_CHROMA + depth);
             if (depth == 0 || parent_cr) cbf_cr = dec(C_CBF_CHROMA + depth);
         }
@@ -660,6 +662,7 @@ private:
         }
         int mode_y = modes_y_[part_nxn_ ? (((y0 - cu_y_) >= (1 << (cu_log2_ - 1))) * 2 + ((x0 - cu_x_) >= (1 << (cu_log2_ - 1)))) : 0];
         emit_tb(x0, y0, log2, 0, mode_y, cbf_luma);
+        if (mono_) return;                          // no chroma TB, no deferred 4x4 pair at blkIdx 3
         if (log2 > 2) {
             emit_tb(x0 >> 1, y0 >> 1, log2 - 1, 1, mode_c_, cbf_cb);
             emit_tb(x0 >> 1, y0 >> 1, log2 - 1, 2, mode_c_, cbf_cr);
@@ -843,6 +846,7 @@ private:
     PictureRecords& out_;
     int W_ = 0, log2ctb_ = 0, min_cb_w_ = 0, min_cb_h_ = 0, w4_ = 0, h4_ = 0;
     int qp_bd_y_ = 0, qp_bd_c_ = 0;
+    bool mono_ = false;                             // ChromaArrayType 0 (chroma_format_idc 0)
     std::vector<int> ctb_slice_;
     std::vector<uint8_t> ct_depth_;
     std::vector<int8_t> qp_map_;
@@ -867,7 +871,10 @@ private:
 }  // namespace
 
 void decode_picture(const Active& act, const std::vector<SliceRef>& slices, PictureRecords& out) {
-    if (act.sps.chroma_format_idc != 1) throw Unsupported("chroma_format_idc != 1 (4:2:0 only)");
+    // ChromaArrayType 1 (4:2:0) and 0 (4:0:0, monochrome); three separately coded colour planes are three
+    // monochrome pictures per access unit (colour_plane_id), which nothing here assembles yet
+    if (act.sps.separate_colour_plane) throw Unsupported("separate_colour_plane_flag = 1 (separately coded colour planes)");
+    if (act.sps.chroma_format_idc > 1) throw Unsupported("chroma_format_idc 2 / 3 (4:2:0 and 4:0:0 only)");
     if (act.sps.range_extension_flags || act.pps.range_extension_flags)
         throw Unsupported("range extension coding tools");
     out = PictureRecords{};

@@ -545,7 +545,7 @@ SliceHeader parse_slice_header(BitReader& br, int nal_type, const std::shared_pt
         }
         if (sps.sao) {
             h.sao_luma = br.flag();
-            if (sps.chroma_format_idc != 0) h.sao_chroma = br.flag();
+            if (sps.chroma_format_idc != 0 && !sps.separate_colour_plane) h.sao_chroma = br.flag();   // ChromaArrayType != 0
         }
         h.slice_qp_delta = br.se();
         h.slice_qp_y = pps.init_qp + h.slice_qp_delta;

@@ -32,8 +32,8 @@ namespace p265r {
 __device__ __forceinline__ Geo pic_geo(Geo g, uint32_t wh) {
     g.w = (int)(wh & 0xffffu);
     g.h = (int)(wh >> 16);
-    g.cw = g.w >> 1;
-    g.ch = g.h >> 1;
+    g.cw = g.mono ? 0 : g.w >> 1;
+    g.ch = g.mono ? 0 : g.h >> 1;
     g.wc = (g.w + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
     g.hc = (g.h + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
     g.nf_w = (g.w + 7) >> 3;
@@ -206,6 +206,7 @@ __global__ __launch_bounds__(64) void intra_step_kernel(const DevPic* __restrict
 
     // ---- neighbour rows/columns from the picture planes -------------------------
     for (int c = 0; c < 3; ++c) {
+        if (c && g.mono) continue;                      // monochrome: no chroma planes (uniform)
         const int sub = c ? 1 : 0;
         const int cs = ctb >> sub;
         const int W = c ? g.cw : g.w, H = c ? g.ch : g.h;
@@ -451,6 +452,7 @@ __global__ __launch_bounds__(64) void intra_step_kernel(const DevPic* __restrict
 
     // ---- write the CTU back to the picture planes (clipped to the picture) -----------
     for (int c = 0; c < 3; ++c) {
+        if (c && g.mono) continue;                      // (wv, hv < 0 below would pass the loop's test)
         const int sub = c ? 1 : 0;
         const int cs = ctb >> sub;
         const int W = c ? g.cw : g.w, H = c ? g.ch : g.h;

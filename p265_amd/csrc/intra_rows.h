@@ -946,7 +946,8 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
     // row units per picture: (cy, luma), (cy, chroma); split: two workgroups per picture, workgroup
-    // parity = the component chain it runs (4:2:0 intra never couples them: no cross-workgroup sync)
+    // parity = the component chain it runs (4:2:0 intra never couples them: no cross-workgroup sync);
+    // split 2 (monochrome): luma rows only, one workgroup per picture slot
     const int units = split ? g.hc : 2 * g.hc;
     // progress words: one per (slot, CTU row, component) in either mode (host: launch_rows_w lds_of)
     const int prog_bytes = (fs_count * 2 * g.hc * 4 + 15) & ~15;
@@ -979,9 +980,11 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
     for (int i = threadIdx.x; i < 35 * 64; i += 64 * W) atab[35 * 16 + i] = angtab_entry<3>(i >> 6, i & 63);
     __syncthreads();
 
-    const int G = split ? (int)(gridDim.x >> 1) : (int)gridDim.x;
-    const int b = split ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
-    const int split_comp = (int)(blockIdx.x & 1u);
+    // split 2 (monochrome): luma rows only -- the split layout's row queue (units = hc, one chain per
+    // workgroup) with one workgroup per picture and comp = 0; a workgroup may hold several pictures in turn
+    const int G = (split & 1) ? (int)(gridDim.x >> 1) : (int)gridDim.x;
+    const int b = (split & 1) ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
+    const int split_comp = (int)(blockIdx.x & 1u) & split;
     const int n_my = b < n_pics ? (n_pics - b + G - 1) / G : 0;
     const int rows_total = XG ? g.hc : n_my * units;
     // XG: this workgroup's chain (picture, component)

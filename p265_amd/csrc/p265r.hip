@@ -72,7 +72,7 @@ int hip_fail(hipError_t e, const char* what) {
 constexpr size_t kDlHalf = 24u << 20;   // download bounce buffer half (p265r_batch_download)
 
 bool params_ok(const p265r_params& p) {
-    return p.version == P265R_ABI_VERSION && p.chroma_format_idc == 1 && p.pic_width > 0 && p.pic_height > 0 &&
+    return p.version == P265R_ABI_VERSION && p.chroma_format_idc <= 1 && p.pic_width > 0 && p.pic_height > 0 &&
            p.pic_width % 8 == 0 && p.pic_height % 8 == 0 && p.ctb_log2_size >= 4 && p.ctb_log2_size <= 6 &&
            p.min_tb_log2_size >= 2 && p.max_tb_log2_size <= 5 && p.min_tb_log2_size <= p.max_tb_log2_size;
 }
@@ -108,6 +108,9 @@ struct p265r_ctx {
     int xg = 4;                // workgroups per chain of the cross-group row kernel (P265R_XG; 0: off; launch_rows)
     bool last_split = false;   // the last row-kernel launch was split (p265r_describe)
     bool last_xg = false;      // ... was the cross-group kernel
+    const char* last_layout = "none";   // row layout of the last run's intra phase: whole | split | xg | luma
+                                        // (monochrome) | steps (per-diagonal kernel) | none (p265r_describe)
+    int last_row_waves = 0;    // ... and the W of its row-kernel build (0: no row kernel ran)
     long long row_launches[4] = {0, 0, 0, 0};      // row-kernel launches per build: W = 12, W = 8, W = 16 split,
                                                    // cross-group -- p265r_describe
     int luma_lead = -1;        // rows the luma chain leads the chroma chain in the row queue (P265R_LUMA_LEAD);
@@ -253,7 +256,8 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
     // picture slots: the W rows in flight are consecutive in the queue, so they span at
     // most ceil(W / hc) + 1 pictures; a slot is reused only after its previous picture is
     // complete (the kernel waits for that, so fewer slots would still be correct)
-    int fs = std::min(32, (W + 2 * g.hc - 1) / (2 * g.hc) + 1);     // 2 row units (luma, chroma) per CTU row
+    const int chains = g.mono ? 1 : 2;                              // row units per CTU row: luma, chroma (Cb + Cr)
+    int fs = std::min(32, (W + chains * g.hc - 1) / (chains * g.hc) + 1);
     auto lds_of = [&](int f) { return rows_lds_bytes<T>(g, W, f); };
     while (fs > 2 && lds_of(fs) > 160 * 1024) --fs;
     auto fn = intra_rows_kernel<W, WPE, XG, TRCHK, T>;
@@ -269,7 +273,8 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
         // component split: a picture's luma chain and its chroma chain on two workgroups of their own
         // (on different CUs) when all of them fit at once -- the latency regime of a few large
         // pictures / tile units, where one workgroup's W waves on one CU bound the picture's time
-        split = ctx->split && pc1 >= 1 && 2 * (long long)b->n_pics <= (long long)pc1 * ctx->num_cus;
+        // (monochrome has one chain per picture: nothing to split; its layout is `luma`, below)
+        split = !g.mono && ctx->split && pc1 >= 1 && 2 * (long long)b->n_pics <= (long long)pc1 * ctx->num_cus;
         if (XG) { fs = 1; split = true; }
     }
     const size_t lds = lds_of(fs);
@@ -282,7 +287,8 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
     // fair CU sharing pairs the two workgroups of a CU (rank = arrival order & 1): only valid
     // when exactly two fit per CU and all of them are resident for the whole launch (grid <= 2
     // per CU, no workgroup starts after another ends) -- and only worth it for a batch alone
-    g.fair = g.fair && alone && per_cu == 2 && !split;
+    g.fair = g.fair && alone && per_cu == 2 && !split && !g.mono;     // (monochrome: the priority bands of the
+                                                                      // one-chain row queue use s_setprio instead)
     // (XG: the progress words were cleared with the CU slots this run, so one tag serves every run)
     const XgBuf xb{XG ? b->d_xg_prog : nullptr, XG ? b->d_xg_lines : nullptr,
                    XG ? b->d_xg_prog + 2 * (size_t)g.hc * b->n_pics : nullptr, XG ? ctx->xg : 0, 1};
@@ -296,9 +302,14 @@ int launch_rows_w(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
     }
 #endif
     const int lead = ctx->luma_lead >= 0 ? ctx->luma_lead : (alone ? 8 : 5);
-    fn<<<grid, 64 * W, lds, st>>>(b->d_pics, b->d_pool, b->d_res, g, b->n_pics, fs, lead, b->d_err, dbg, split ? 1 : 0, xb);
+    // layout (the kernel's `split` argument): 0 whole pictures (luma and chroma rows interleaved), 1 component
+    // split (two workgroups per picture), 2 luma rows only (monochrome: one workgroup per picture slot)
+    const int layout = g.mono ? 2 : (split ? 1 : 0);
+    fn<<<grid, 64 * W, lds, st>>>(b->d_pics, b->d_pool, b->d_res, g, b->n_pics, fs, lead, b->d_err, dbg, layout, xb);
     ctx->last_split = split;
     ctx->last_xg = XG;
+    ctx->last_layout = XG ? "xg" : (layout == 2 ? "luma" : (layout == 1 ? "split" : "whole"));
+    ctx->last_row_waves = W;
     ++ctx->row_launches[XG ? 3 : (W == 16 ? 2 : (W == 8 ? 1 : 0))];
     HIP_TRY(hipGetLastError());
 #ifdef P265R_DEBUG_DIAG
@@ -328,14 +339,15 @@ int launch_rows(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
                        : launch_rows_w<8, 1, false, false, uint16_t>(ctx, b, st, alone);
     }
     // the smallest batches (every chain on xg CUs of its own): the cross-group kernel, one wave per SIMD
-    if (ctx->row_waves == 0 && b->d_xg_prog && 2 * (long long)b->n_pics * ctx->xg <= ctx->num_cus)
+    if (ctx->row_waves == 0 && !ctx->geo.mono && b->d_xg_prog && 2 * (long long)b->n_pics * ctx->xg <= ctx->num_cus)
         return ctx->geo.tr_check ? launch_rows_w<4, 1, true, true>(ctx, b, st, alone)     // (test build of it)
                                  : launch_rows_w<4, 1, true>(ctx, b, st, alone);
     // a batch small enough for the component split with one workgroup per CU (the latency regime:
     // tile units, the decoder's small batches): W = 16, so every CTU row of a picture's chain can
     // be in flight at once (a 2-CTU-lag wavefront of 17 rows needs 17 waves; with 12 the rows
     // after the 12th wait for a whole row to finish)
-    if (ctx->row_waves == 0 && ctx->split && 2 * (long long)b->n_pics <= ctx->num_cus)
+    // (monochrome: one chain per picture, so up to one picture per CU)
+    if (ctx->row_waves == 0 && ctx->split && (ctx->geo.mono ? 1 : 2) * (long long)b->n_pics <= ctx->num_cus)
         return launch_rows_w<16, 4>(ctx, b, st, alone);
     const int w = ctx->row_waves ? ctx->row_waves : (alone ? 12 : 8);
     return w == 12 ? launch_rows_w<12, 6>(ctx, b, st, alone) : launch_rows_w<8, 6>(ctx, b, st, alone);
@@ -406,7 +418,29 @@ int launch_export(const p265r_export_desc& d, const DevPic* d_pics, const Geo& g
         return dim3((unsigned)((mw / group + 2 + kExportLanes - 1) / kExportLanes),
                     (unsigned)((row_units + kExportRows - 1) / kExportRows), (unsigned)n);
     };
-    if (d.format == P265R_FMT_PLANAR) {
+    if (g.mono) {
+        // monochrome: luma rows alone (semi-planar: + the grey CbCr rows); RGB one row per unit, no upsampling
+        const int grey = (1 << (g.bd[0] - 1)) << a.shift;
+        if (d.format == P265R_FMT_PLANAR) {
+            export_mono_yuv_kernel<S, false><<<grid(16 / (int)sizeof(S), mh), 256, 0, st>>>(d_pics, g, a, grey);
+        } else if (d.format == P265R_FMT_SEMIPLANAR) {
+            export_mono_yuv_kernel<S, true><<<grid(16 / (int)sizeof(S), mh + mh / 2), 256, 0, st>>>(d_pics, g, a, grey);
+        } else {
+            auto rgb = [&](auto dtag) {
+                using D = typename decltype(dtag)::type;
+                if (d.format == P265R_FMT_RGB_PACKED)
+                    export_mono_rgb_kernel<S, D, true><<<grid(sizeof(D) == 1 ? 16 : 8, mh), 256, 0, st>>>(d_pics, g, a);
+                else
+                    export_mono_rgb_kernel<S, D, false><<<grid(sizeof(D) == 1 ? 16 : 8, mh), 256, 0, st>>>(d_pics, g, a);
+            };
+            switch (d.sample) {
+                case P265R_SMP_U8: rgb(std::enable_if<true, uint8_t>{}); break;
+                case P265R_SMP_F16: rgb(std::enable_if<true, _Float16>{}); break;
+                case P265R_SMP_F32: rgb(std::enable_if<true, float>{}); break;
+                default: rgb(std::enable_if<true, S>{}); break;                   // NATIVE
+            }
+        }
+    } else if (d.format == P265R_FMT_PLANAR) {
         export_yuv_kernel<S, false><<<grid(16 / (int)sizeof(S), 2 * mh), 256, 0, st>>>(d_pics, g, a);
     } else if (d.format == P265R_FMT_SEMIPLANAR) {
         export_yuv_kernel<S, true><<<grid(16 / (int)sizeof(S), mh + mh / 2), 256, 0, st>>>(d_pics, g, a);
@@ -473,7 +507,10 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     if (!params_ok(p)) return P265R_EINVAL;
     // BitDepth 8 (uint8_t planes) or 9..12 with one depth for luma and chroma (uint16_t planes; 13..14 would
     // need SaoOffsetVal beyond the int8 of the CTU record)
-    if (p.bit_depth_luma < 8 || p.bit_depth_luma > 12 || p.bit_depth_chroma != p.bit_depth_luma || p.scaling_list_enabled > 1)
+    // (monochrome, chroma_format_idc 0: bit_depth_chroma, the chroma QP offsets and a scaling table's chroma
+    // entries mean nothing and are ignored)
+    const bool mono = p.chroma_format_idc == 0;
+    if (p.bit_depth_luma < 8 || p.bit_depth_luma > 12 || (!mono && p.bit_depth_chroma != p.bit_depth_luma) || p.scaling_list_enabled > 1)
         return P265R_EUNSUPPORTED;
     const int n = p265r_device_count();
     if (n < 0) return n;
@@ -482,21 +519,26 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     if (!ctx) return P265R_ENOMEM;
     ctx->device = device;
     ctx->params = p;
+    if (mono) {                                     // one depth from here on; no chroma QP
+        ctx->params.bit_depth_chroma = p.bit_depth_luma;
+        ctx->params.pps_cb_qp_offset = ctx->params.pps_cr_qp_offset = 0;
+    }
     Geo& g = ctx->geo;
     g.w = p.pic_width; g.h = p.pic_height;
-    g.cw = g.w / 2; g.ch = g.h / 2;
+    g.mono = mono ? 1 : 0;
+    g.cw = mono ? 0 : g.w / 2; g.ch = mono ? 0 : g.h / 2;
     g.stride[0] = (int)align_up(g.w, 64);
     g.stride[1] = g.stride[2] = (int)align_up(g.cw, 64);
     g.ctb_log2 = p.ctb_log2_size;
     g.wc = (g.w + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
     g.hc = (g.h + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
-    g.bd[0] = p.bit_depth_luma; g.bd[1] = g.bd[2] = p.bit_depth_chroma;
+    g.bd[0] = p.bit_depth_luma; g.bd[1] = g.bd[2] = ctx->params.bit_depth_chroma;
     g.pel16 = p.bit_depth_luma > 8 ? 1 : 0;
     g.strong = p.strong_intra_smoothing;
     g.lf_tiles = p.loop_filter_across_tiles;
     g.nf_w = (g.w + 7) / 8;
-    g.cqp[0] = p.pps_cb_qp_offset;
-    g.cqp[1] = p.pps_cr_qp_offset;
+    g.cqp[0] = ctx->params.pps_cb_qp_offset;
+    g.cqp[1] = ctx->params.pps_cr_qp_offset;
     g.fair = 1;
     if (const char* v = std::getenv("P265R_FAIR")) g.fair = v[0] != '0';
     g.quad = 3;
@@ -765,7 +807,7 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
         const Geo& g = ctx->geo;
         const size_t pb = plan.pel_bytes;
         for (int i = 0; i < n_pics && e == hipSuccess; ++i)
-            for (int c = 0; c < 3 && e == hipSuccess; ++c) {
+            for (int c = 0; c < (g.mono ? 1 : 3) && e == hipSuccess; ++c) {
                 const size_t wd = (size_t)(plan.psize[i][0] >> (c ? 1 : 0)), ht = (size_t)(plan.psize[i][1] >> (c ? 1 : 0));
                 e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, pics[i].recon[c], wd * pb, wd * pb, ht, hipMemcpyHostToDevice, st);
                 b->h2d_bytes += wd * pb * ht;
@@ -881,7 +923,7 @@ int run_residual_prep(p265r_ctx* ctx, p265r_batch* b, const Geo& g, const RunPla
         // waves start before the residual kernels fill the chip
         // (tr_info: launch_rows' latency layouts, the cross-group kernel and the W = 16 split, need 2 n_pics <= CUs)
         Geo gp = g;
-        gp.tr_info = 2 * (long long)b->n_pics <= ctx->num_cus ? 1 : 0;
+        gp.tr_info = (g.mono ? 1 : 2) * (long long)b->n_pics <= ctx->num_cus ? 1 : 0;
         intra_prep_kernel<<<dim3(g.wc, g.hc, b->n_pics), 64, 0, ps>>>(b->d_pics, gp, b->view);
         ++tm->residual_launches;
         if (ps != s) HIP_TRY(hipEventRecord(ctx->join_ev[li], ps));
@@ -945,6 +987,7 @@ int run_intra(p265r_ctx* ctx, p265r_batch* b, const Geo& g, const RunPlan& rp, p
         ++tm->intra_launches;
     }
     const int n_steps = (rp.recon && ctx->schedule == 0) ? (g.wc - 1) + 2 * (g.hc - 1) + 1 : 0;
+    if (n_steps) { ctx->last_layout = "steps"; ctx->last_row_waves = 0; }
     for (int step = 0; step < n_steps; ++step) {
         const int d = step - (g.wc - 1);
         const int cy_min = d > 0 ? (d + 1) / 2 : 0;
@@ -1045,7 +1088,7 @@ int p265r_batch_download(p265r_ctx* ctx, p265r_batch* b, const p265r_picture* pi
     std::vector<Item> items;
     const int pb = g.pel16 ? 2 : 1;                          // bytes per sample
     for (int i = 0; i < n_pics; ++i)
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < (g.mono ? 1 : 3); ++c) {      // (monochrome: out[1..2] / recon[1..2] are never touched)
             const int sub = c ? 1 : 0;
             const int w = (b->size[i][0] >> sub) * pb, h = b->size[i][1] >> sub;     // (w in bytes)
             const int pitch = (c ? g.stride[1] : g.stride[0]) * pb;
@@ -1134,7 +1177,8 @@ int p265r_batch_digest(p265r_ctx* ctx, p265r_batch* b, int which, uint64_t* out,
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), sizeof(uint64_t) * (size_t)n));
     hipError_t e = hipMemsetAsync(d, 0, sizeof(uint64_t) * (size_t)n, b->stream);
     if (e == hipSuccess) {
-        const dim3 grid((unsigned)((ctx->geo.h + kDigestRows - 1) / kDigestRows), 3, (unsigned)b->n_pics);
+        // (monochrome: no block for planes 1 and 2, whose entries stay zero)
+        const dim3 grid((unsigned)((ctx->geo.h + kDigestRows - 1) / kDigestRows), ctx->geo.mono ? 1 : 3, (unsigned)b->n_pics);
         digest_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, which == 0 ? 1 : 0, d);
         e = hipGetLastError();
     }
@@ -1155,7 +1199,7 @@ int p265r_batch_digest_async(p265r_ctx* ctx, p265r_batch* b, int which, int slot
     }
     unsigned long long* d = b->d_dig + 3 * (size_t)b->n_pics * slot;
     HIP_TRY(hipMemsetAsync(d, 0, per_slot, b->stream));
-    const dim3 grid((unsigned)((ctx->geo.h + kDigestRows - 1) / kDigestRows), 3, (unsigned)b->n_pics);
+    const dim3 grid((unsigned)((ctx->geo.h + kDigestRows - 1) / kDigestRows), ctx->geo.mono ? 1 : 3, (unsigned)b->n_pics);
     digest_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, which == 0 ? 1 : 0, d);
     HIP_TRY(hipGetLastError());
     ctx->lane_busy |= 1u << b->lane;
@@ -1182,11 +1226,14 @@ int p265r_batch_hash_async(p265r_ctx* ctx, p265r_batch* b, int hash_type) {
     if (!b->d_hash) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_hash), out_bytes + acc_bytes));
     uint4* out = reinterpret_cast<uint4*>(b->d_hash);
     uint32_t* acc = reinterpret_cast<uint32_t*>(b->d_hash + out_bytes);
+    // monochrome: no chain or block for planes 1 and 2; their 16 bytes are zero
+    const int hashed = ctx->geo.mono ? 1 : 3;
+    if (ctx->geo.mono) HIP_TRY(hipMemsetAsync(out, 0, out_bytes, b->stream));
     if (hash_type == P265R_HASH_MD5) {
-        hash_md5_kernel<<<dim3((unsigned)((n_planes + 63) / 64)), 64, 0, b->stream>>>(b->d_pics, ctx->geo, b->n_pics, out);
+        hash_md5_kernel<<<dim3((unsigned)((hashed * b->n_pics + 63) / 64)), 64, 0, b->stream>>>(b->d_pics, ctx->geo, b->n_pics, out);
     } else {
         HIP_TRY(hipMemsetAsync(acc, 0, acc_bytes, b->stream));
-        const dim3 grid((unsigned)((ctx->geo.h + kHashRows - 1) / kHashRows), 3, (unsigned)b->n_pics);
+        const dim3 grid((unsigned)((ctx->geo.h + kHashRows - 1) / kHashRows), (unsigned)hashed, (unsigned)b->n_pics);
         if (hash_type == P265R_HASH_CRC) hash_crc_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, acc);
         else hash_checksum_kernel<<<grid, 256, 0, b->stream>>>(b->d_pics, ctx->geo, acc);
         HIP_TRY(hipGetLastError());
@@ -1230,7 +1277,7 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
     // ---- host checks: nothing is launched unless all of them pass ----------------------------
     const int B = ctx->params.bit_depth_luma;
     ExportShape shape;
-    if (const int rc = export_check_desc(*desc, B, &shape)) return rc;
+    if (const int rc = export_check_desc(*desc, B, &shape, ctx->geo.mono != 0)) return rc;
     std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
     uint64_t slot_bytes = 0;
     int mw = 0, mh = 0;
@@ -1267,7 +1314,9 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
     for (int k = 0; k < 3; ++k) { a.plane_off[k] = desc->plane_off[k]; a.pitch[k] = desc->pitch[k]; }
     a.crop_l = desc->crop_left; a.crop_r = desc->crop_right; a.crop_t = desc->crop_top; a.crop_b = desc->crop_bottom;
     if (shape.rgb) {
-        if (const int rc = export_coefficients(*desc, B, a.coef)) return rc;
+        p265r_export_desc dc = *desc;                       // (the coefficients do not depend on the crop; a
+        dc.crop_left = dc.crop_right = dc.crop_top = dc.crop_bottom = 0;   // monochrome one may be odd)
+        if (const int rc = export_coefficients(dc, B, a.coef)) return rc;
         a.fscale = (float)(1.0 / (double)((1 << B) - 1));
     }
     a.shift = desc->sample == P265R_SMP_MSB16 ? 16 - B : 0;
@@ -1375,6 +1424,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
         "\"experiments_build\": %d, \"split\": %d, \"last_launch_split\": %d, \"xg\": %d, \"last_launch_xg\": %d, "
         "\"phase_order\": %d, \"early_residual\": %d, \"bit_depth\": %d, \"row_launches\": {\"w12\": %lld, \"w8\": %lld, \"w16_split\": %lld, \"xg\": %lld, \"other\": %lld}, "
         "\"sparse_expand\": \"%s\", \"sparse_expand_stream\": %d, \"last_sparse_expand_ms\": %.4f, "
+        "\"chroma_format_idc\": %d, \"last_launch_layout\": \"%s\", \"last_launch_row_waves\": %d, "
         "\"env_overrides\": [%s]}",
         ctx->schedule ? "rows" : "steps", ctx->row_waves,
         ctx->row_waves ? "fixed" : (P265R_PHASE_ORDER
@@ -1399,6 +1449,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
         0, ctx->split, ctx->last_split ? 1 : 0, ctx->xg, ctx->last_xg ? 1 : 0, P265R_PHASE_ORDER, P265R_EARLY_RESIDUAL,
         (int)ctx->params.bit_depth_luma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], 0ll,
         "lds tile", 0, ctx->last_expand_ms,
+        (int)ctx->params.chroma_format_idc, ctx->last_layout, ctx->last_row_waves,
         ctx->describe.c_str());
     if (n < 0) return P265R_EINVAL;
     if (size > 0) {

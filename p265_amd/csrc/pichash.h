@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void hash_crc_kernel(const DevPic* __restrict_
 __global__ __launch_bounds__(64) void hash_final_kernel(const DevPic* __restrict__ pics, Geo g, int crc, int n_planes,
                                                         const uint32_t* __restrict__ acc, uint4* __restrict__ out) {
     const int pl = blockIdx.x * 64 + threadIdx.x;
-    if (pl >= n_planes) return;
+    if (pl >= n_planes || (g.mono && pl % 3)) return;   // (monochrome: planes 1 and 2 stay zero)
     uint32_t v = acc[pl];
     uint32_t word;
     if (crc) {
@@ -178,7 +178,7 @@ __device__ __forceinline__ void hash_md5_fetch(const HashPlane& hp, uint32_t wpr
 __global__ __launch_bounds__(64) void hash_md5_kernel(const DevPic* __restrict__ pics, Geo g, int n_pics,
                                                       uint4* __restrict__ out) {
     const int idx = blockIdx.x * 64 + threadIdx.x;
-    if (idx >= 3 * n_pics) return;
+    if (idx >= (g.mono ? 1 : 3) * n_pics) return;        // (monochrome: the luma chains alone)
     const int c = idx / n_pics, pic = idx - c * n_pics;
     const HashPlane hp = hash_plane(pics[pic], g, c);
     const uint32_t wpr = (uint32_t)hp.rb >> 2, n_words = wpr * (uint32_t)hp.h;

@@ -47,7 +47,8 @@ int validate_picture(const p265r_params& p, const Geo& geo, const p265r_picture&
     const int n_ctus = g.wc * g.hc;
     if (!pic.ctus || (!pic.tbs && pic.n_tbs) || (!pic.coef && pic.n_coef)) return P265R_EINVAL;
     if (pic.flags & ~P265R_PIC_RECON_INPUT) return P265R_EINVAL;
-    if ((pic.flags & P265R_PIC_RECON_INPUT) && (!pic.recon[0] || !pic.recon[1] || !pic.recon[2])) return P265R_EINVAL;
+    // (monochrome: the reconstruction is the luma plane alone; recon[1..2] are never read)
+    if ((pic.flags & P265R_PIC_RECON_INPUT) && (!pic.recon[0] || (!geo.mono && (!pic.recon[1] || !pic.recon[2])))) return P265R_EINVAL;
     const int ctb = 1 << p.ctb_log2_size;
     const int max_tbs = 3 * (ctb / 4) * (ctb / 4) / 2;                  // all-4x4 luma + 4x4 chroma per 8x8
     for (int rs = 0; rs < n_ctus; ++rs) {
@@ -65,6 +66,8 @@ int validate_picture(const p265r_params& p, const Geo& geo, const p265r_picture&
         }
         // Cb and Cr share SaoTypeIdx and SaoEoClass (7.4.9.3.2; sao.py:57-59, 75-77)
         if (c.sao_type[1] != c.sao_type[2] || (c.sao_type[1] == 2 && c.sao_class[1] != c.sao_class[2])) return P265R_EINVAL;
+        // monochrome (ChromaArrayType 0): no chroma SAO, no chroma TB (the kernels have no plane to put them in)
+        if (geo.mono && (c.sao_type[1] | c.sao_type[2])) return P265R_EINVAL;
         const int cx0 = (rs % g.wc) * ctb, cy0 = (rs / g.wc) * ctb;
         int n_luma = 0, n_chroma = 0;
         for (uint32_t i = c.tb_begin; i < c.tb_begin + c.tb_count; ++i) {
@@ -72,6 +75,7 @@ int validate_picture(const p265r_params& p, const Geo& geo, const p265r_picture&
             if (t.c_idx == 0 && ++n_luma > (ctb / 4) * (ctb / 4)) return P265R_EINVAL;   // intra_prep.h kMaxCtuLuma
             if (t.c_idx && ++n_chroma > 2 * (ctb / 8) * (ctb / 8)) return P265R_EINVAL;  // kMaxCtuChroma
             if (!tb_fields_ok(p, t) || t.pred_mode > 34) return P265R_EINVAL;
+            if (geo.mono && t.c_idx) return P265R_EINVAL;
             if (t.c_idx && t.log2_size > 4) return P265R_EINVAL;        // 4:2:0 chroma TBs are 4..16
             const int sub = t.c_idx ? 1 : 0;
             const int n = 1 << t.log2_size;
@@ -134,7 +138,7 @@ int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool sp
                 if (rc) { crc[i] = rc; return; }
             }
             if (!(tb.flags & (P265R_TB_CBF | P265R_TB_PCM))) continue;
-            if (!tb_fields_ok(p, tb)) { crc[i] = P265R_EINVAL; return; }
+            if (!tb_fields_ok(p, tb) || (g.mono && tb.c_idx)) { crc[i] = P265R_EINVAL; return; }
             if (!tb_coef_ok(tb, pic.n_coef, sp != nullptr)) { crc[i] = P265R_ERANGE; return; }
             const int cls = tb_class(tb);
             cp[cls] += (size_t)1 << (2 * tb.log2_size);
@@ -187,6 +191,8 @@ int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool sp
     u.pel_bytes = g.pel16 ? 2 : 1;               // bytes per sample
     const size_t pb = u.pel_bytes, nc = (size_t)n_ctus;
     const size_t plane_bytes[3] = {(size_t)g.stride[0] * g.h * pb, (size_t)g.stride[1] * g.ch * pb, (size_t)g.stride[2] * g.ch * pb};
+    // (monochrome: plane_bytes[1..2] = 0 -- a picture is its luma plane; plane_off[1..2] are unused)
+    u.mono = g.mono != 0;
     u.plane_off[0] = 0;
     u.plane_off[1] = align_up(plane_bytes[0], 256);
     u.plane_off[2] = u.plane_off[1] + align_up(plane_bytes[1], 256);
@@ -196,7 +202,7 @@ int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool sp
     // error word (+ the row kernel's per-CU workgroup slots, kRowCuSlots x 16 B, intra_rows.h)
     // cross-group row kernel (a batch whose chains fit xg workgroups each on the CUs): its progress words
     // follow the CU slots (cleared together per run), its lines get their own range
-    u.xg_ok = xg > 0 && split && 2 * (long long)n_pics * xg <= num_cus;
+    u.xg_ok = !g.mono && xg > 0 && split && 2 * (long long)n_pics * xg <= num_cus;   // (not offered to monochrome)
     // (+ one row ticket per chain)
     const size_t xg_prog_bytes = u.xg_ok ? sizeof(int) * 2 * ((size_t)g.hc + 1) * n_pics : 0;
     u.o_err = off; off = align_up(off + 256 + kRowCuSlots * 16 + xg_prog_bytes, 256);
@@ -349,6 +355,7 @@ void pack_picture(const UploadPlan& u, int i, const p265r_picture* pics, const p
     for (int c = 0; c < 3; ++c) {
         dp.rec[c] = dbase + u.o_rec + u.pic_plane_bytes * i + u.plane_off[c];
         dp.out[c] = u.lf ? dbase + u.o_out + u.pic_plane_bytes * i + u.plane_off[c] : dp.rec[c];
+        if (u.mono && c) dp.rec[c] = dp.out[c] = nullptr;            // no chroma planes exist
     }
     if (pic.nofilter) {
         std::memcpy(stage + u.s_nf + u.nf_at[i] * u.nf_bytes, pic.nofilter, u.pnf[i]);   // (slot of the context size)

@@ -69,6 +69,7 @@ struct UploadPlan {
     int n_pics = 0;
     int nc = 0;                        // per-picture CTU slots (the context size)
     bool sparse = false, recon_input = false, ragged = false, sao = false, dbk = false, lf = false, xg_ok = false;
+    bool mono = false;            // Geo::mono: a picture's planes are its luma plane alone
     // per picture: luma size, CTUs, no-filter map bytes (a ragged batch mixes sizes)
     std::vector<std::array<int, 2>> psize;
     std::vector<int> pnc;

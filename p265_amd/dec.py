@@ -9,7 +9,9 @@ line compatibility (this decoder writes no syntax logs).  Parsing runs on host t
 (bounded memory) and the YUV written in output order as pictures complete.  ``--format nv12|p010|rgb24|
 rgb-planar-f16`` (with ``--matrix``, ``--full-range``, ``--upsample`` for RGB) converts on the GPU and writes the
 exported frames; the default ``i420`` is the host path.  ``--hash-on device`` checks the decoded picture hash SEI
-on the GPU instead of on downloaded planes.
+on the GPU instead of on downloaded planes.  A monochrome (4:0:0) stream writes luma-only frames by default;
+``--mono-output i420`` appends chroma planes of 1 << (BitDepth - 1), and the GPU formats take their one-plane
+forms (nv12 / p010: a grey CbCr plane; RGB: R = G = B).
 """
 import argparse
 import sys
@@ -42,6 +44,9 @@ def parse_cmd(argv=None):
     ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default="bt709", help="RGB formats: the YCbCr matrix")
     ap.add_argument("--full-range", action="store_true", help="RGB formats: full-range YCbCr (default limited)")
     ap.add_argument("--upsample", choices=("nearest", "bilinear"), default="nearest", help="RGB formats: chroma upsampling")
+    ap.add_argument("--mono-output", choices=("y", "i420"), default="y",
+                    help="a monochrome (4:0:0) stream with the default --format: luma-only frames (y), or I420 frames "
+                         "whose chroma planes are 1 << (BitDepth - 1) (i420)")
     return ap.parse_args(argv)
 
 
@@ -57,7 +62,7 @@ def main(argv=None):
     t0 = time.time()
     st = decoder.decode_file(a.bitstream, a.output, device=a.device, batch=a.batch, threads=a.threads,
                              depth=a.depth, verify_hash=not a.no_verify, sparse_upload=a.sparse_upload,
-                             export=export_spec(a), hash_on=a.hash_on)
+                             export=export_spec(a), hash_on=a.hash_on, mono_output=a.mono_output)
     dt = time.time() - t0
     print("decoded %d pictures in %.3f s; picture hash SEI checked %d, mismatched %d"
           % (st["pictures"], dt, st["hash_checked"], st["hash_mismatch"]))

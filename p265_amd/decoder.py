@@ -34,19 +34,21 @@ class DecodedFrame:
     poc: int
     output_rank: int
     decode_index: int
-    planes: list                 # full decoded Y, Cb, Cr (uint8; uint16 above 8 bits), pic_width x pic_height
+    planes: list                 # full decoded Y, Cb, Cr (uint8; uint16 above 8 bits), pic_width x pic_height;
+                                 # a monochrome (4:0:0) stream: [Y]
     crop: tuple                  # (left, right, top, bottom) luma samples
     hash_ok: Optional[bool]      # None: stream carries no picture hash for this picture
     device: object = None        # export=...: recon.DeviceFrame, this frame cropped and converted in device memory
                                  # (its batch's buffer is freed when the last frame of the batch is released or
                                  # collected); planes is then None unless the picture hashes were verified on the host
+    bit_depth: int = 8           # BitDepthY of the stream (the grey of a monochrome picture's missing chroma)
 
     def cropped(self):
         l, r, t, b = self.crop
         y = self.planes[0]
         h, w = y.shape
         out = [y[t:h - b, l:w - r]]
-        for c in (1, 2):
+        for c in range(1, len(self.planes)):     # (monochrome: the luma plane alone, any crop parity)
             out.append(self.planes[c][t // 2:(h - b) // 2, l // 2:(w - r) // 2])
         return out
 
@@ -338,13 +340,14 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
         for k, (d, planes) in enumerate(zip(group, outs)):
             fr = DecodedFrame(poc=d.poc, output_rank=-1, decode_index=int(d.picture.meta["decode_index"]),
                               planes=planes, crop=tuple(int(v) for v in d.crop), hash_ok=None,
-                              device=frames.slot(k) if frames is not None else None)
+                              device=frames.slot(k) if frames is not None else None,
+                              bit_depth=int(d.params["bit_depth_luma"]))
             futs = None
             if hashes is not None:
                 nb = len(d.hash[0])
-                fr.hash_ok = all(hashes[k, c, :nb].tobytes() == d.hash[c] for c in range(3))
+                fr.hash_ok = all(hashes[k, c, :nb].tobytes() == d.hash[c] for c in range(len(d.hash)))
             elif d.hash is not None and planes is not None and not device_hash:
-                futs = [pool.submit(bitstream.plane_hash, planes[c], d.hash_type) for c in range(3)]
+                futs = [pool.submit(bitstream.plane_hash, planes[c], d.hash_type) for c in range(len(d.hash))]
             ready += outq.push((fr, d, futs), d.cvs_id, d.poc, d.max_num_reorder, d.output_flag)
         return ready
 
@@ -424,9 +427,21 @@ def _file_chunks(path, chunk):
             yield b
 
 
-def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CHUNK, **kw) -> dict:
+def grey_chroma(fr: DecodedFrame):
+    """The two chroma planes a 4:2:0 consumer expects beside a monochrome frame's cropped luma: ceil(W / 2) x
+    ceil(H / 2) samples of 1 << (BitDepth - 1) each."""
+    y = fr.cropped()[0]
+    c = np.full(((y.shape[0] + 1) // 2, (y.shape[1] + 1) // 2), 1 << (fr.bit_depth - 1), y.dtype)
+    return [c, c]
+
+
+def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CHUNK, mono_output: str = "y", **kw) -> dict:
     """Stream a bitstream file to a cropped I420 YUV file in output order; returns counts.  With ``export=`` the
-    file holds the exported frames instead (one device-to-host copy per batch, no host crop or interleave)."""
+    file holds the exported frames instead (one device-to-host copy per batch, no host crop or interleave).
+    A monochrome (4:0:0) stream writes luma-only frames; ``mono_output="i420"`` appends grey chroma planes
+    (grey_chroma) on the host path."""
+    if mono_output not in ("y", "i420"):
+        raise ValueError("mono_output: 'y' or 'i420', not %r" % (mono_output,))
     n = checked = bad = 0
     f = open(output, "wb") if output else None
     try:
@@ -438,7 +453,10 @@ def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CH
             if f and fr.device is not None:
                 f.write(fr.device.tobytes())
             elif f:
-                for p in fr.cropped():
+                planes = fr.cropped()
+                if len(planes) == 1 and mono_output == "i420":
+                    planes = planes + grey_chroma(fr)
+                for p in planes:
                     f.write(np.ascontiguousarray(p).tobytes())
             if fr.device is not None:
                 fr.device.release()
@@ -449,7 +467,7 @@ def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CH
 
 
 def write_yuv(frames: List[DecodedFrame], path: str):
-    """Planar 4:2:0 8-bit YUV (I420), cropped, in output order."""
+    """Planar 4:2:0 YUV (I420), cropped, in output order; the frames of a monochrome stream: Y only."""
     with open(path, "wb") as f:
         for fr in frames:
             for p in fr.cropped():

@@ -101,6 +101,7 @@ def rccl_ranks():
 def broadcast_params(params, src=0):
     """Broadcast the params POD (records.PARAMS_DTYPE) from ``src`` to every rank:
     ncclBroadcast of its 32 bytes on a hipMalloc'd buffer, or over the control plane."""
+    R.require_420(params, "dist.broadcast_params")
     g = _group
     if g is None or (g.world == 1 and g.nccl is None):
         return params

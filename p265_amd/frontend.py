@@ -64,6 +64,9 @@ class PictureBuilder:
 
     def __init__(self, params, pcm_loop_filter_disabled=False):
         self.params = params
+        # monochrome (chroma_format_idc 0, ChromaArrayType 0): no chroma TB, PCM sample or SAO record exists;
+        # the chroma arguments of add_cu / add_ctu are ignored
+        self.mono = R.is_mono(params)
         self.wc, self.hc = R.ctb_grid(params)
         self.ctb_log2 = int(params["ctb_log2_size"])
         self.ctus = np.zeros(self.wc * self.hc, R.CTU_DTYPE)
@@ -111,7 +114,7 @@ class PictureBuilder:
         if bypass or (pcm and self.pcm_lf_disabled):
             self._mark_nofilter(x, y, log2)
         if pcm:
-            for c in range(3):
+            for c in range(1 if self.mono else 3):
                 lg = log2 if c == 0 else log2 - 1
                 sub = 0 if c == 0 else 1
                 off = self._store(pcm_samples[c])
@@ -123,6 +126,8 @@ class PictureBuilder:
             tx, ty, tl = int(t["x"]), int(t["y"]), int(t["log2"])
             pu = (((ty - y) >= half) * 2 + ((tx - x) >= half)) if part_mode == 1 else 0
             self._emit(addr, tx, ty, tl, 0, int(modes_y[pu]), t, 0, qp_y, byp)
+            if self.mono:
+                continue
             if tl > 2:
                 for c, qp in ((1, qp_cb), (2, qp_cr)):
                     self._emit(addr, tx >> 1, ty >> 1, tl - 1, c, mode_c, t, c, qp, byp)
@@ -155,7 +160,7 @@ class PictureBuilder:
         c["tile_id"] = tile_id
         c["flags"] = (R.CTU_LF_ACROSS_SLICES if lf_across_slices else 0) | (R.CTU_DEBLOCK if deblocking else 0)
         c["deblock_offsets"] = R.deblock_offsets(int(beta_offset_div2), int(tc_offset_div2)) if deblocking else 0
-        for ci in range(3):
+        for ci in range(1 if self.mono else 3):
             t = int(sao_type[ci])
             c["sao_type"][ci] = t
             if t == 0:
@@ -210,7 +215,7 @@ class ReconHook:
         self.params = params
         self.off_y, self.off_c = qp_bd_offset_y, qp_bd_offset_c
         self.pcm_shift = (int(params["bit_depth_luma"]) - int(pcm_bit_depth_luma),
-                          int(params["bit_depth_chroma"]) - int(pcm_bit_depth_chroma))
+                          0 if R.is_mono(params) else int(params["bit_depth_chroma"]) - int(pcm_bit_depth_chroma))
         self.pcm_lf_disabled = bool(pcm_loop_filter_disabled)
         self.builder = PictureBuilder(params, pcm_loop_filter_disabled=self.pcm_lf_disabled)
         self.pictures = []
@@ -219,6 +224,8 @@ class ReconHook:
         n = int(cu.size)
         h = n >> 1
         luma = np.asarray(cu.pcm_sample_luma, np.int64).reshape(n, n) << self.pcm_shift[0]
+        if R.is_mono(self.params):               # no pcm_sample_chroma at ChromaArrayType 0 (7.3.8.7)
+            return [luma.astype(np.int16), None, None]
         ch = np.asarray(cu.pcm_sample_chroma, np.int64).reshape(2, h, h) << self.pcm_shift[1]
         return [luma.astype(np.int16), ch[0].astype(np.int16), ch[1].astype(np.int16)]
 

@@ -35,6 +35,7 @@ class TileGrid:
     """Tile columns / rows in CTBs (6.5.1), for one picture size."""
 
     def __init__(self, params, cols, rows):
+        R.require_420(params, "halo.TileGrid")
         self.params = params
         self.ctb_log2 = int(params["ctb_log2_size"])
         self.ctb = 1 << self.ctb_log2

@@ -54,8 +54,7 @@ def sparsify(pic):
 
 
 def plane_shapes(params):
-    w, h = int(params["pic_width"]), int(params["pic_height"])
-    return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
+    return R.plane_shapes(params)
 
 
 class DecodedPicture:
@@ -139,12 +138,14 @@ class ExportLayout:
     """A filled p265r_export_desc plus what Python needs to view a frame slot: the element dtype and, per
     picture size, the shape and byte strides of every destination plane."""
 
-    def __init__(self, desc, bit_depth):
+    def __init__(self, desc, bit_depth, mono=False):
         self.desc = desc
         native = np.dtype(np.uint16 if bit_depth > 8 else np.uint8)
         self.dtype = {_lib.SMP_NATIVE: native, _lib.SMP_MSB16: np.dtype(np.uint16), _lib.SMP_U8: np.dtype(np.uint8),
                       _lib.SMP_F16: np.dtype(np.float16), _lib.SMP_F32: np.dtype(np.float32)}[desc.sample]
-        self.n_planes = {_lib.FMT_PLANAR: 3, _lib.FMT_SEMIPLANAR: 2, _lib.FMT_RGB_PLANAR: 3, _lib.FMT_RGB_PACKED: 1}[desc.format]
+        # (a monochrome source: planar is the Y plane alone; semi-planar keeps its CbCr plane, written mid-grey)
+        self.n_planes = {_lib.FMT_PLANAR: 1 if mono else 3, _lib.FMT_SEMIPLANAR: 2, _lib.FMT_RGB_PLANAR: 3,
+                         _lib.FMT_RGB_PACKED: 1}[desc.format]
         self.plane_off = [int(desc.plane_off[k]) for k in range(self.n_planes)]
         self.pitch = [int(desc.pitch[k]) for k in range(self.n_planes)]
         self.frame_bytes = int(desc.frame_bytes)
@@ -172,7 +173,7 @@ def export_layout(params, spec, size=None):
     w, h = (0, 0) if size is None else (int(size[0]), int(size[1]))
     _lib.check(_lib.load().p265r_export_layout(ctypes.byref(pc), w, h, ctypes.byref(d), int(spec.pitch_align)),
                "p265r_export_layout")
-    return ExportLayout(d, int(params["bit_depth_luma"]))
+    return ExportLayout(d, int(params["bit_depth_luma"]), mono=R.is_mono(params))
 
 
 def export_coefficients(spec, bit_depth):
@@ -386,7 +387,7 @@ class ReconContext:
                 nf = np.ascontiguousarray(p.nofilter, np.uint8)
                 keep.append(nf)
                 c.nofilter = nf.ctypes.data
-            for k in range(3):
+            for k in range(R.n_planes(self.params)):
                 if outs is not None:
                     c.out[k] = outs[i][k].ctypes.data
                 if recons is not None:
@@ -394,7 +395,7 @@ class ReconContext:
             if p.recon_input is not None:
                 c.flags = R.PIC_RECON_INPUT
                 dts = R.plane_dtypes(self.params)
-                planes = [np.ascontiguousarray(p.recon_input[k], dts[k]) for k in range(3)]
+                planes = [np.ascontiguousarray(p.recon_input[k], dts[k]) for k in range(len(dts))]
                 for k, (pl, shp) in enumerate(zip(planes, plane_shapes(pp))):
                     if pl.shape != shp:
                         raise R.RecordError("recon_input plane %d has shape %s, expected %s" % (k, pl.shape, shp))
@@ -454,7 +455,7 @@ class ReconContext:
             if len(into) != n:
                 raise ValueError("into: one entry per picture")
             for i in sel:
-                for k in range(3):
+                for k in range(len(dts)):
                     a = into[i][k]
                     if a.shape != tuple(shp[i][k]) or a.dtype != dts[k] or not a.flags.c_contiguous or not a.flags.writeable:
                         raise ValueError("into: picture %d plane %d does not match the plane layout" % (i, k))
@@ -465,7 +466,7 @@ class ReconContext:
                 if with_recon else None)
         arr = (_lib.PictureC * n)()
         for i in sel:
-            for k in range(3):
+            for k in range(len(dts)):
                 arr[i].out[k] = outs[i][k].ctypes.data
                 if recs is not None:
                     arr[i].recon[k] = recs[i][k].ctypes.data
@@ -530,12 +531,13 @@ class ReconContext:
         return out
 
     def picture_hash(self, batch, hash_type):
-        """hash_async + hash_read: per picture three ``bytes`` (Y, Cb, Cr) of the SEI's length (16, 2 or 4)."""
+        """hash_async + hash_read: per picture three ``bytes`` (Y, Cb, Cr) of the SEI's length (16, 2 or 4);
+        a monochrome context: one (Y)."""
         if int(hash_type) not in _lib.HASH_BYTES:
             raise _lib.P265RError(_lib.EINVAL, "p265r_batch_hash_async")
         self.hash_async(batch, hash_type)
         nb = _lib.HASH_BYTES[int(hash_type)]
-        return [[h[c, :nb].tobytes() for c in range(3)] for h in self.hash_read(batch)]
+        return [[h[c, :nb].tobytes() for c in range(R.n_planes(self.params))] for h in self.hash_read(batch)]
 
     # ---- device-side output -----------------------------------------------------------
     def export_layout(self, spec, pic=None):

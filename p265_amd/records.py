@@ -64,12 +64,39 @@ def make_params(**kw) -> np.ndarray:
     return p
 
 
+def is_mono(params) -> bool:
+    """chroma_format_idc 0 (4:0:0, ChromaArrayType 0): a picture is its luma plane alone."""
+    return int(params["chroma_format_idc"]) == 0
+
+
+def n_planes(params) -> int:
+    """Planes of a decoded picture: 3 (Y, Cb, Cr), or 1 (Y) for monochrome params."""
+    return 1 if is_mono(params) else 3
+
+
+def require_420(params, what):
+    """The tile, halo and multi-rank paths handle three planes: monochrome params are refused by name."""
+    if is_mono(params):
+        raise ValueError("%s: monochrome (chroma_format_idc 0) pictures are not supported here; decode them as "
+                         "whole pictures (recon.ReconContext, decoder.decode_*)" % what)
+
+
 def plane_dtypes(params):
     """numpy sample type of the Y, Cb, Cr planes: uint8 at BitDepth 8, uint16 (little-endian) above
-    (include/p265r.h p265r_picture.out / recon)."""
+    (include/p265r.h p265r_picture.out / recon).  Monochrome params: the Y plane alone."""
     dy = np.uint8 if int(params["bit_depth_luma"]) <= 8 else np.uint16
+    if is_mono(params):
+        return [dy]
     dc = np.uint8 if int(params["bit_depth_chroma"]) <= 8 else np.uint16
     return [dy, dc, dc]
+
+
+def plane_shapes(params):
+    """[y][x] shapes of the planes plane_dtypes() lists (4:2:0 chroma: half size each way)."""
+    w, h = int(params["pic_width"]), int(params["pic_height"])
+    if is_mono(params):
+        return [(h, w)]
+    return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
 
 
 def qp_bd_offset(params, c_idx=0) -> int:
@@ -314,6 +341,11 @@ def validate(params, pic: Picture):
         raise RecordError("coefficient range outside coef array")
     if (pic.ctus["sao_type"] > 2).any():
         raise RecordError("bad SaoTypeIdx")
+    if is_mono(params):
+        if (c > 0).any():
+            raise RecordError("chroma TB in a monochrome picture")
+        if (pic.ctus["sao_type"][:, 1:] != 0).any():
+            raise RecordError("chroma SaoTypeIdx in a monochrome picture")
     st, sc = pic.ctus["sao_type"], pic.ctus["sao_class"]
     if ((st[:, 1] != st[:, 2]) | ((st[:, 1] == 2) & (sc[:, 1] != sc[:, 2]))).any():
         raise RecordError("Cb and Cr must share SaoTypeIdx and SaoEoClass (7.4.9.3.2)")

@@ -15,6 +15,7 @@ from . import records as R
 
 def tile_grid(params, pic):
     """Column/row boundaries (in CTBs) of the tiles, recovered from the CTU tile ids."""
+    R.require_420(params, "tiles.tile_grid")
     wc, hc = R.ctb_grid(params)
     tid = pic.ctus["tile_id"].astype(np.int64).reshape(hc, wc)
     cols = [0] + [x for x in range(1, wc) if tid[0, x] != tid[0, x - 1]] + [wc]
@@ -28,6 +29,7 @@ def split(params, pic, recon_only=False):
     With loop_filter_across_tiles_enabled_flag = 1 a tile's in-loop filters need its
     neighbours' samples: split then only serves the reconstruction pass (``recon_only``:
     in-loop filter flags cleared) and p265_amd/halo.py does the filtering."""
+    R.require_420(params, "tiles.split")
     if int(params["loop_filter_across_tiles"]) and not recon_only:
         raise NotImplementedError("loop_filter_across_tiles_enabled_flag=1: split(recon_only=True) + halo.py")
     if recon_only:
@@ -95,6 +97,7 @@ def ragged_params(parts):
 
 def stitch(params, tiles, planes_per_tile):
     """Assemble decoded tile planes ([Y, Cb, Cr] per tile) into full-picture planes."""
+    R.require_420(params, "tiles.stitch")
     w, h = int(params["pic_width"]), int(params["pic_height"])
     out = [np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8)]
     for (tp, _, (x0, y0)), planes in zip(tiles, planes_per_tile):
