@@ -3,11 +3,14 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 # -structurizecfg-skip-uniform-regions: uniform branches stay plain scalar branches (no i1 flow masks in
 # SGPR pairs): row kernel 4.70 -> 4.21 ms per 512 1080p pictures (tools/ab_libs2.sh, round 3)
+# Do not add -ffp-contract=fast (here or through `make variant FLAGS=`): resize_math.h's rs_norm keeps its fp32 multiply
+# and add apart with `#pragma clang fp contract(off)`, which hipcc's default fast-honor-pragmas respects and `fast` overrides
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wall -Wno-unused-function -mllvm -structurizecfg-skip-uniform-regions=true
 # (sparse_host.cpp, upload_host.cpp: the host-only parts of the upload, plain C++ -- see sparse-check, upload-check;
-# export_host.cpp: the host-only part of the device-side output; pichash_host.cpp: the picture hash of a host plane)
+# export_host.cpp, resize_host.cpp: the host-only parts of the device-side output and its scaled form;
+# pichash_host.cpp: the picture hash of a host plane)
 SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/export_host.cpp \
-       p265_amd/csrc/pichash_host.cpp
+       p265_amd/csrc/pichash_host.cpp p265_amd/csrc/resize_host.cpp
 HDR := $(wildcard p265_amd/csrc/*.h) include/p265r.h
 
 CXX ?= g++
@@ -46,7 +49,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check tools/resize_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -94,6 +97,15 @@ hash-check: tools/hash_check.cpp p265_amd/csrc/pichash_host.cpp p265_amd/csrc/pi
 		-o tools/hash_check tools/hash_check.cpp p265_amd/csrc/pichash_host.cpp
 	./tools/hash_check
 .PHONY: hash-check
+
+# host sanitizer check of the scaled device-side output's host code (resize_math.h through resize_plane_host against a
+# brute-force restatement, the reciprocal division, malformed descriptors): a stand-alone CPU program, not part of `all`
+resize-check: tools/resize_check.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/export_host.cpp p265_amd/csrc/resize_host.h \
+              p265_amd/csrc/resize_math.h p265_amd/csrc/export_host.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o tools/resize_check tools/resize_check.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/export_host.cpp
+	./tools/resize_check
+.PHONY: resize-check
 
 # experiment builds: make variant V=name FLAGS="-DX=1"  ->  p265_amd/libp265r_name.so
 variant:

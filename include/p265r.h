@@ -325,6 +325,80 @@ int  p265r_export_coefficients(const p265r_export_desc* desc, int bit_depth, int
 int  p265r_batch_export(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
                         void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index, int n);
 
+/* ---- scaled device-side output: every frame slot out_width x out_height -------------------------------------
+ * No counterpart in the reference.  The SOURCE of a frame is the crop window of its picture (own size, as
+ * above): W x H luma samples with origin (l, t); a chroma plane's window is W/2 x H/2 at (l/2, t/2).  Taps are
+ * clamped to THE WINDOW, not to the decoded picture: a resized frame is a function of its window alone
+ * (deliberately unlike P265R_UP_BILINEAR above, which reads decoded chroma outside the window).
+ * desc->upsample is ignored: the filter decides how chroma is sampled.
+ *
+ * Per axis: n = luma window length, m = luma output length, step = floor((n << 16) / m).  An output sample sits
+ * at half-sample coordinate h of the output LUMA grid, U(h) = (h * step) >> 1 its source position x 2^16 in luma
+ * samples from the window's edge (h * step <= 2 n << 16: below 2^32, U below 2^31).
+ *   output on the luma grid (Y planes; R, G, B), index i:       h = 2 i + 1 on both axes
+ *   output on the chroma grid (planar / semi-planar Cb, Cr of a 4:2:0 source), index j:
+ *                                                               h = 4 j + 1 horizontally, 4 j + 2 vertically
+ *   (chroma_sample_loc_type 0: co-sited left, vertically midway).  n_p = n for a luma plane, n / 2 for chroma.
+ * NEAREST   luma plane: index min(U >> 16, n - 1); chroma plane: min((U >> 16) >> 1, n / 2 - 1).  At m = n the
+ *   result is byte-identical to p265r_batch_export with P265R_UP_NEAREST.
+ * BILINEAR  pos = U - 32768 (luma plane); (U - 32768) >> 1 (chroma, horizontal); (U - 65536) >> 1 (chroma,
+ *   vertical); arithmetic shifts; pos clamped to [0, (n_p - 1) << 16]; i0 = pos >> 16, i1 = min(i0 + 1, n_p - 1),
+ *   f = (pos >> 8) & 255.  Value, int32, with a, b the taps i0, i1 of row i0 and c, d those of row i1:
+ *     (((256 - fx) a + fx b) (256 - fy) + ((256 - fx) c + fx d) fy + 32768) >> 16.   Upscaling is legal.
+ * AREA      exact box average, downscale only (m <= n on both axes).  In units of 1 / m of a luma sample,
+ *   luma-grid output i covers [i n, (i + 1) n) and plane sample k covers [k e m, (k + 1) e m), e = 1 for luma and
+ *   2 for chroma: chroma counts as two luma samples wide and high, its horizontal quarter-sample siting is
+ *   ignored.  Chroma-grid outputs: the same with the plane's own n / 2, m / 2 and e = 1.  A sample's weight is
+ *   the length of the overlap; the weights of one output sum to N, the covered length (n, or n / 2).
+ *     value = (sum_y sum_x wy wx s + (Nx Ny >> 1)) / (Nx Ny), unsigned 64-bit, floor division.
+ *   Windows of at most 8192 samples per axis (else P265R_EINVAL): the sum stays below 2^38, Nx Ny <= 2^26.
+ * After the filter the planes are at output resolution and the arithmetic of p265r_batch_export applies unchanged
+ * (MSB16 shift, CbCr interleave, the integer RGB conversion and clip, a monochrome source's R = G = B and grey
+ * CbCr).  Float outputs: out = fl32(fl32(float(v) * scale[c]) + bias[c]), two separately rounded fp32 operations
+ * (never one fma); F16 = that value rounded to nearest even.  Without P265R_RS_NORM scale[c] = float(1 / (2^B - 1))
+ * and bias[c] = 0: the plain export's value. */
+#define P265R_RS_NEAREST  0u
+#define P265R_RS_BILINEAR 1u
+#define P265R_RS_AREA     2u     /* exact box average; downscale only */
+#define P265R_RS_NORM     1u     /* flags: scale[] / bias[] are used (F16 / F32 samples only) */
+
+typedef struct p265r_resize_desc {
+    uint32_t out_width, out_height;   /* 1 .. 16384; even for planar / semi-planar output of a 4:2:0 source
+                                         and for semi-planar output of a monochrome source */
+    uint32_t filter;                  /* P265R_RS_* */
+    uint32_t flags;                   /* 0 | P265R_RS_NORM */
+    float    scale[3], bias[3];       /* per output channel (R, G, B or Y, Cb, Cr order of the format) */
+} p265r_resize_desc;
+
+/* host only, no context: like p265r_export_layout, but the layout of an out_width x out_height frame (it does
+ * not depend on a picture's size); validates desc and rs (P265R_EINVAL: an unknown filter or flag bit, a size of
+ * 0 or above 16384, an odd size where the format has half-size chroma, P265R_RS_NORM with a sample type other
+ * than F16 / F32, a non-finite scale or bias) */
+int  p265r_resize_layout(const p265r_params* params, p265r_export_desc* desc, const p265r_resize_desc* rs,
+                         uint32_t pitch_align);
+/* host only: the source position of the output sample at half-sample coordinate h along one axis, as the kernels
+ * compute it: n, m the luma window and output lengths, chroma = 1 for a chroma plane, vertical = 1 for the
+ * vertical axis.  NEAREST: *i0 = *i1 = the index, *frac = 0; BILINEAR: i0, i1, f.  P265R_EINVAL for P265R_RS_AREA
+ * (it has weights, not a position), n or m outside 1 .. 32767 / 16384, h outside 0 .. 2 m, an odd n with chroma. */
+int  p265r_resize_position(uint32_t filter, int n, int m, int h, int chroma, int vertical,
+                           int32_t* i0, int32_t* i1, int32_t* frac);
+/* host only: the scalar reference of one plane through the arithmetic the kernels use (for tests).  src = the
+ * plane's window origin (uint16 samples, stride samples between rows), nw x nh the LUMA window, mw x mh the LUMA
+ * output size; chroma_plane: src is a chroma plane (nw / 2 x nh / 2); chroma_grid: the output is on the chroma grid
+ * (mw / 2 x mh / 2, else mw x mh).  dst: the values, tight.  norm = {scale, bias} (or NULL): f32_out / f16_out
+ * (each optional) get the float outputs of those values, fp16 as its 16 bits. */
+int  p265r_resize_plane_host(const uint16_t* src, uint64_t stride, int nw, int nh, int chroma_plane, int chroma_grid,
+                             uint32_t filter, int mw, int mh, int32_t* dst, const float* norm, float* f32_out,
+                             uint16_t* f16_out);
+/* as p265r_batch_export, every frame slot out_width x out_height: one kernel launch on the batch's lane, no
+ * stream of its own, every check on the host before the launch.  The refusals of p265r_batch_export (the layout
+ * is checked against the output size), those of p265r_resize_layout, and P265R_EINVAL for a crop window of ANY listed
+ * picture above 32767 samples on an axis (every filter: the 32-bit position arithmetic), and for P265R_RS_AREA with an
+ * output dimension larger than such a window or a window above 8192. */
+int  p265r_batch_export_resized(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
+                                const p265r_resize_desc* rs, void* dev_dst, uint64_t dst_bytes,
+                                const int32_t* pic_index, int n);
+
 /* ---- device-side picture hash: the decoded_picture_hash SEI values (D.3.19) computed in device memory ----
  * No counterpart in the reference (no SEI support, nalu.py:130-131).  The hash of a plane runs over its
  * pictureData: the samples of the picture's OWN size (uncropped) in raster order, one byte per sample at

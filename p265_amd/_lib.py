@@ -77,6 +77,15 @@ class ExportDesc(ctypes.Structure):
                 ("frame_bytes", ctypes.c_uint64)]
 
 
+class ResizeDesc(ctypes.Structure):
+    """p265r_resize_desc (scaled device-side output)."""
+    _fields_ = [("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32), ("filter", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+
+# p265r_resize_desc filters and flags
+RS_NEAREST, RS_BILINEAR, RS_AREA = 0, 1, 2
+RS_NORM = 1
 # p265r_export_desc enums (include/p265r.h)
 FMT_PLANAR, FMT_SEMIPLANAR, FMT_RGB_PLANAR, FMT_RGB_PACKED = 0, 1, 2, 3
 SMP_NATIVE, SMP_MSB16, SMP_U8, SMP_F16, SMP_F32 = 0, 1, 2, 3, 4
@@ -87,6 +96,7 @@ HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
 HASH_BYTES = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 
 assert ctypes.sizeof(Params) == 32 and ctypes.sizeof(PictureC) == 104 and ctypes.sizeof(ExportDesc) == 88
+assert ctypes.sizeof(ResizeDesc) == 40
 
 # every symbol include/p265r.h declares, with (restype, argtypes)
 _vp = ctypes.c_void_p
@@ -112,6 +122,15 @@ SIGNATURES = {
     "p265r_export_coefficients": (ctypes.c_int, [ctypes.POINTER(ExportDesc), ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
     "p265r_batch_export": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), _vp, ctypes.c_uint64,
                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    "p265r_resize_layout": (ctypes.c_int, [ctypes.POINTER(Params), ctypes.POINTER(ExportDesc), ctypes.POINTER(ResizeDesc),
+                                           ctypes.c_uint32]),
+    "p265r_resize_position": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "p265r_resize_plane_host": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "p265r_batch_export_resized": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), ctypes.POINTER(ResizeDesc), _vp,
+                                                  ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
     "p265r_batch_hash_async": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "p265r_batch_hash_read": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]),
     "p265r_plane_hash_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,

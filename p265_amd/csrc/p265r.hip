@@ -23,6 +23,8 @@
 #include "digest.h"
 #include "export.h"
 #include "export_host.h"
+#include "resize.h"
+#include "resize_host.h"
 #include "intra.h"
 #include "intra_prep.h"
 #include "intra_rows.h"
@@ -464,6 +466,48 @@ int launch_export(const p265r_export_desc& d, const DevPic* d_pics, const Geo& g
             case P265R_SMP_F16: by_shape(std::enable_if<true, _Float16>{}); break;
             case P265R_SMP_F32: by_shape(std::enable_if<true, float>{}); break;
             default: by_shape(std::enable_if<true, S>{}); break;                  // NATIVE
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// The one launch of p265r_batch_export_resized on stream st: n slots of a.ow x a.oh.
+template <typename S>
+int launch_resize(const p265r_export_desc& d, uint32_t filter, const DevPic* d_pics, const Geo& g, const ResizeArgs& a, int n,
+                  hipStream_t st) {
+    const auto blocks = [](int rows) { return (rows + kExportRows - 1) / kExportRows; };
+    const auto grid = [&](int group, int row_blocks) {
+        return dim3((unsigned)((a.ow / group + 2 + kExportLanes - 1) / kExportLanes), (unsigned)row_blocks, (unsigned)n);
+    };
+    const auto by_filter = [&](auto&& go) {
+        if (filter == P265R_RS_NEAREST) go(std::integral_constant<int, (int)kRsNearest>{});
+        else if (filter == P265R_RS_BILINEAR) go(std::integral_constant<int, (int)kRsBilinear>{});
+        else go(std::integral_constant<int, (int)kRsArea>{});
+    };
+    if (d.format == P265R_FMT_PLANAR || d.format == P265R_FMT_SEMIPLANAR) {
+        const int semi = d.format == P265R_FMT_SEMIPLANAR ? 1 : 0;
+        const int chroma_blocks = semi ? blocks(a.oh / 2) : (g.mono ? 0 : 2 * blocks(a.oh / 2));
+        by_filter([&](auto f) {
+            resize_yuv_kernel<S, decltype(f)::value><<<grid(16 / (int)sizeof(S), blocks(a.oh) + chroma_blocks), 256, 0, st>>>(
+                d_pics, g, a, semi);
+        });
+    } else {
+        auto rgb = [&](auto dtag) {
+            using D = typename decltype(dtag)::type;
+            by_filter([&](auto f) {
+                constexpr int F = decltype(f)::value;
+                if (d.format == P265R_FMT_RGB_PACKED)
+                    resize_rgb_kernel<S, D, true, F><<<grid(sizeof(D) == 1 ? 16 : 8, blocks(a.oh)), 256, 0, st>>>(d_pics, g, a);
+                else
+                    resize_rgb_kernel<S, D, false, F><<<grid(sizeof(D) == 1 ? 16 : 8, blocks(a.oh)), 256, 0, st>>>(d_pics, g, a);
+            });
+        };
+        switch (d.sample) {
+            case P265R_SMP_U8: rgb(std::enable_if<true, uint8_t>{}); break;
+            case P265R_SMP_F16: rgb(std::enable_if<true, _Float16>{}); break;
+            case P265R_SMP_F32: rgb(std::enable_if<true, float>{}); break;
+            default: rgb(std::enable_if<true, S>{}); break;                       // NATIVE
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1330,6 +1374,73 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
     }
     const int rc = ctx->geo.pel16 ? launch_export<uint16_t>(*desc, b->d_pics, ctx->geo, a, mw, mh, n, b->stream)
                                   : launch_export<uint8_t>(*desc, b->d_pics, ctx->geo, a, mw, mh, n, b->stream);
+    if (rc) return rc;
+    ctx->lane_busy |= 1u << b->lane;
+    return P265R_OK;
+}
+
+int p265r_batch_export_resized(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* desc, const p265r_resize_desc* rs,
+                               void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index, int n) {
+    if (!ctx || !b || !desc || !rs || !dev_dst) return P265R_EINVAL;
+    if (!pic_index) n = b->n_pics;
+    if (n <= 0 || n > b->n_pics || n > 65535) return P265R_EINVAL;
+    // ---- host checks: nothing is launched unless all of them pass ----------------------------
+    const int B = ctx->params.bit_depth_luma;
+    ExportShape shape;
+    if (const int rc = resize_check_desc(*desc, *rs, B, ctx->geo.mono != 0, &shape)) return rc;
+    uint64_t slot_bytes = 0;
+    if (const int rc = resize_check_layout(*desc, shape, *rs, &slot_bytes)) return rc;
+    std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
+    for (int i = 0; i < n; ++i) {
+        const int pic = pic_index ? pic_index[i] : i;
+        if (pic < 0 || pic >= b->n_pics) return P265R_EINVAL;
+        if (pic_index) {
+            if (seen[(size_t)pic]) return P265R_EINVAL;
+            seen[(size_t)pic] = 1;
+        }
+        // every listed picture's own window against the filter (a ragged batch: per picture)
+        if (const int rc = resize_check_window(*rs, b->size[(size_t)pic][0] - desc->crop_left - desc->crop_right,
+                                               b->size[(size_t)pic][1] - desc->crop_top - desc->crop_bottom))
+            return rc;
+    }
+    if ((uint64_t)(uintptr_t)dev_dst % (uint64_t)shape.es) return P265R_EINVAL;
+    const uint64_t need = (uint64_t)(n - 1) * desc->frame_bytes + slot_bytes;
+    if (b->runs == 0) return P265R_ESTATE;                  // (a recon-input batch whose filters never ran: no planes yet)
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto on_device = [&](const void* p) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+    };
+    if (!on_device(dev_dst)) return P265R_EINVAL;
+    if (need > dst_bytes) return P265R_ERANGE;
+    if (!on_device(static_cast<const unsigned char*>(dev_dst) + need - 1)) return P265R_EINVAL;
+    // ---- enqueue ---------------------------------------------------------------------------------
+    ResizeArgs a{};
+    a.e.dst = static_cast<uint8_t*>(dev_dst);
+    a.e.frame_bytes = desc->frame_bytes;
+    for (int k = 0; k < 3; ++k) { a.e.plane_off[k] = desc->plane_off[k]; a.e.pitch[k] = desc->pitch[k]; }
+    a.e.crop_l = desc->crop_left; a.e.crop_r = desc->crop_right; a.e.crop_t = desc->crop_top; a.e.crop_b = desc->crop_bottom;
+    if (shape.rgb) {
+        p265r_export_desc dc = *desc;                       // (the coefficients depend on neither crop nor upsample)
+        dc.crop_left = dc.crop_right = dc.crop_top = dc.crop_bottom = 0;
+        dc.upsample = P265R_UP_NEAREST;
+        if (const int rc = export_coefficients(dc, B, a.e.coef)) return rc;
+    }
+    a.e.shift = desc->sample == P265R_SMP_MSB16 ? 16 - B : 0;
+    a.ow = (int)rs->out_width; a.oh = (int)rs->out_height;
+    a.grey = (1 << (B - 1)) << a.e.shift;
+    resize_norm(*rs, B, a.scale, a.bias);
+    if (pic_index) {
+        // the list's device copy lives until the lane is next synchronised (the kernel reads it in stream order)
+        void* d_idx = nullptr;
+        HIP_TRY(hipMalloc(&d_idx, sizeof(int32_t) * (size_t)n));
+        b->exp_idx.push_back(d_idx);
+        HIP_TRY(hipMemcpy(d_idx, pic_index, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        a.e.pic_index = static_cast<const int32_t*>(d_idx);
+    }
+    const int rc = ctx->geo.pel16 ? launch_resize<uint16_t>(*desc, rs->filter, b->d_pics, ctx->geo, a, n, b->stream)
+                                  : launch_resize<uint8_t>(*desc, rs->filter, b->d_pics, ctx->geo, a, n, b->stream);
     if (rc) return rc;
     ctx->lane_busy |= 1u << b->lane;
     return P265R_OK;

@@ -11,7 +11,9 @@ rgb-planar-f16`` (with ``--matrix``, ``--full-range``, ``--upsample`` for RGB) c
 exported frames; the default ``i420`` is the host path.  ``--hash-on device`` checks the decoded picture hash SEI
 on the GPU instead of on downloaded planes.  A monochrome (4:0:0) stream writes luma-only frames by default;
 ``--mono-output i420`` appends chroma planes of 1 << (BitDepth - 1), and the GPU formats take their one-plane
-forms (nv12 / p010: a grey CbCr plane; RGB: R = G = B).
+forms (nv12 / p010: a grey CbCr plane; RGB: R = G = B).  ``--resize WxH`` (with ``--resize-filter nearest|bilinear|
+area``) scales every frame of a GPU format to that size on the GPU (the scaled device-side output); the default
+``i420`` host path does not scale and refuses both.
 """
 import argparse
 import sys
@@ -47,14 +49,33 @@ def parse_cmd(argv=None):
     ap.add_argument("--mono-output", choices=("y", "i420"), default="y",
                     help="a monochrome (4:0:0) stream with the default --format: luma-only frames (y), or I420 frames "
                          "whose chroma planes are 1 << (BitDepth - 1) (i420)")
-    return ap.parse_args(argv)
+    ap.add_argument("--resize", metavar="WxH", default=None,
+                    help="GPU formats: scale every (cropped) frame to W x H on the GPU")
+    ap.add_argument("--resize-filter", choices=("nearest", "bilinear", "area"), default=None,
+                    help="the filter of --resize (default bilinear; area: exact box average, downscale only)")
+    a = ap.parse_args(argv)
+    if a.resize is not None or a.resize_filter is not None:
+        if a.format == "i420":
+            ap.error("--resize / --resize-filter scale on the GPU: choose a GPU --format (%s); the default i420 is the "
+                     "host path and does not scale" % ", ".join(FORMATS[1:]))
+        if a.resize is None:
+            ap.error("--resize-filter needs --resize WxH")
+        try:
+            w, h = (int(v) for v in a.resize.lower().split("x"))
+        except ValueError:
+            ap.error("--resize: WxH, e.g. 224x224")
+        a.resize = (w, h)
+    return a
 
 
 def export_spec(a):
     """The ExportSpec of the parsed command line; None for the default i420 (the host path, unchanged)."""
     if a.format == "i420":
         return None
-    return recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample)
+    kw = {}
+    if a.resize is not None:
+        kw = dict(size=a.resize, resize=a.resize_filter or "bilinear")
+    return recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample, **kw)
 
 
 def main(argv=None):

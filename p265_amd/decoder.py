@@ -190,6 +190,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     ``export``: every batch is also converted on the device right after its run (ReconContext.export, cropped to
     each picture's conformance window; the spec's own crop is ignored) and every frame carries its slot as
     ``DecodedFrame.device``; the planes come back to the host only while ``verify_hash`` is on.
+    An ``ExportSpec(size=(w, h), ...)`` scales every frame to that size on the device (the scaled export): the slots
+    of a batch are then one dense array (``DecodedFrame.device.frames.batch_array()``).
     ``hash_on``: "host" (default) hashes the downloaded planes on the host pool; "device" computes the picture
     hashes of every batch on the GPU behind its run (ReconContext.hash_async; batches are also cut where the
     SEI's hash type changes), reads 48 bytes per picture and never hashes on the host: with ``export`` no

@@ -91,6 +91,7 @@ _SAMPLES = {"native": _lib.SMP_NATIVE, "msb16": _lib.SMP_MSB16, "u8": _lib.SMP_U
             "f32": _lib.SMP_F32}
 _MATRICES = {"bt601": _lib.MAT_BT601, "bt709": _lib.MAT_BT709, "bt2020": _lib.MAT_BT2020}
 _UPSAMPLES = {"nearest": _lib.UP_NEAREST, "bilinear": _lib.UP_BILINEAR}
+_FILTERS = {"nearest": _lib.RS_NEAREST, "bilinear": _lib.RS_BILINEAR, "area": _lib.RS_AREA}
 
 
 @dataclass(frozen=True)
@@ -99,7 +100,10 @@ class ExportSpec:
     native | msb16 | u8 | f16 | f32, and for RGB ``matrix`` bt601 | bt709 | bt2020, ``full_range`` and
     ``upsample`` nearest | bilinear (names, or the P265R_* integers).  ``crop`` = (left, right, top, bottom)
     in luma samples, relative to each picture's own size; ``pitch_align`` > 1 rounds every pitch and plane
-    offset up to it."""
+    offset up to it.  ``size`` = (width, height): the scaled export (p265r_batch_export_resized) -- every frame slot
+    has this size whatever its picture's, the crop window filtered by ``resize`` nearest | bilinear | area (area:
+    downscale only; ``upsample`` is then ignored); ``scale`` / ``bias`` (3-tuples, f16 / f32 samples only): the
+    float outputs are v * scale[c] + bias[c] instead of v / (2^BitDepth - 1)."""
     format: object = "planar"
     sample: object = "native"
     matrix: object = "bt709"
@@ -107,6 +111,10 @@ class ExportSpec:
     upsample: object = "nearest"
     crop: tuple = (0, 0, 0, 0)
     pitch_align: int = 1
+    size: object = None
+    resize: object = "bilinear"
+    scale: object = None
+    bias: object = None
 
     @staticmethod
     def named(name, **kw):
@@ -133,13 +141,37 @@ class ExportSpec:
         d.crop_left, d.crop_right, d.crop_top, d.crop_bottom = (int(v) for v in self.crop)
         return d
 
+    def resize_desc(self):
+        """The p265r_resize_desc of this spec (``size`` set)."""
+        if self.size is None:
+            raise ValueError("size: the (width, height) of the scaled export")
+        r = _lib.ResizeDesc()
+        r.out_width, r.out_height = int(self.size[0]), int(self.size[1])
+        if isinstance(self.resize, str):
+            if self.resize not in _FILTERS:
+                raise ValueError("unknown resize filter %r" % (self.resize,))
+            r.filter = _FILTERS[self.resize]
+        else:
+            r.filter = int(self.resize)
+        if self.scale is not None or self.bias is not None:
+            sc = (1.0, 1.0, 1.0) if self.scale is None else tuple(self.scale)
+            bi = (0.0, 0.0, 0.0) if self.bias is None else tuple(self.bias)
+            if len(sc) != 3 or len(bi) != 3:
+                raise ValueError("scale / bias: one value per output channel (3)")
+            r.flags = _lib.RS_NORM
+            for c in range(3):
+                r.scale[c], r.bias[c] = float(sc[c]), float(bi[c])
+        return r
+
 
 class ExportLayout:
     """A filled p265r_export_desc plus what Python needs to view a frame slot: the element dtype and, per
     picture size, the shape and byte strides of every destination plane."""
 
-    def __init__(self, desc, bit_depth, mono=False):
+    def __init__(self, desc, bit_depth, mono=False, resize=None):
         self.desc = desc
+        self.resize = resize                     # the p265r_resize_desc of a scaled export, else None
+        self.size = (int(resize.out_width), int(resize.out_height)) if resize is not None else None
         native = np.dtype(np.uint16 if bit_depth > 8 else np.uint8)
         self.dtype = {_lib.SMP_NATIVE: native, _lib.SMP_MSB16: np.dtype(np.uint16), _lib.SMP_U8: np.dtype(np.uint8),
                       _lib.SMP_F16: np.dtype(np.float16), _lib.SMP_F32: np.dtype(np.float32)}[desc.sample]
@@ -152,9 +184,12 @@ class ExportLayout:
         self.crop = (desc.crop_left, desc.crop_right, desc.crop_top, desc.crop_bottom)
 
     def plane_view(self, k, size):
-        """(shape, byte strides) of plane ``k`` of a picture of luma ``size`` = (width, height) before the crop."""
+        """(shape, byte strides) of plane ``k`` of a picture of luma ``size`` = (width, height) before the crop; a
+        scaled export: of its output size, whatever the picture's."""
         l, r, t, b = self.crop
         w, h = int(size[0]) - l - r, int(size[1]) - t - b
+        if self.size is not None:
+            w, h = self.size
         es, f = self.dtype.itemsize, self.desc.format
         if f == _lib.FMT_RGB_PACKED:
             return (h, w, 3), (self.pitch[0], 3 * es, es)
@@ -167,9 +202,15 @@ class ExportLayout:
 
 def export_layout(params, spec, size=None):
     """ExportLayout of ``spec`` for pictures of ``size`` = (width, height) (default: the params' size), through
-    the C p265r_export_layout (host only: no context, no device)."""
+    the C p265r_export_layout (host only: no context, no device); with ``spec.size`` the layout of a frame of that
+    size, through p265r_resize_layout."""
     d = spec.desc()
     pc = _params_c(params)
+    if spec.size is not None:
+        rs = spec.resize_desc()
+        _lib.check(_lib.load().p265r_resize_layout(ctypes.byref(pc), ctypes.byref(d), ctypes.byref(rs), int(spec.pitch_align)),
+                   "p265r_resize_layout")
+        return ExportLayout(d, int(params["bit_depth_luma"]), mono=R.is_mono(params), resize=rs)
     w, h = (0, 0) if size is None else (int(size[0]), int(size[1]))
     _lib.check(_lib.load().p265r_export_layout(ctypes.byref(pc), w, h, ctypes.byref(d), int(spec.pitch_align)),
                "p265r_export_layout")
@@ -230,6 +271,31 @@ class DeviceFrames:
         shape, strides = self.layout.plane_view(k, self.sizes[i])
         return DevicePlane(self, self.ptr + i * self.layout.frame_bytes + self.layout.plane_off[k], shape, strides,
                            self.layout.dtype)
+
+    def batch_array(self, k=0):
+        """Plane ``k`` of ALL slots as one ``__cuda_array_interface__``: (n, 3, H, W) for rgb_planar (k = 0: its three
+        planes), (n, H, W, 3) for rgb_packed, (n, H, W) (semi-planar CbCr: (n, H / 2, W / 2, 2)) otherwise.  The strides
+        come from frame_bytes, plane_off and pitch.  ValueError when the slots are not of one size (no ``size`` and a
+        ragged batch) or the R, G, B plane offsets are not evenly spaced."""
+        lay = self.layout
+        if not 0 <= k < lay.n_planes:
+            raise IndexError("plane %d" % k)
+        if not self.sizes:
+            raise ValueError("batch_array: no slots")
+        views = {lay.plane_view(k, s) for s in self.sizes}
+        if len(views) != 1:
+            raise ValueError("batch_array: the slots are not of one size (export with ExportSpec(size=...))")
+        shape, strides = views.pop()
+        off = lay.plane_off[k]
+        if lay.desc.format == _lib.FMT_RGB_PLANAR:
+            if k != 0:
+                raise IndexError("rgb_planar: batch_array(0) holds the three planes")
+            step = lay.plane_off[1] - lay.plane_off[0]
+            if lay.plane_off[2] - lay.plane_off[1] != step or step <= 0 or \
+                    lay.pitch[1] != lay.pitch[0] or lay.pitch[2] != lay.pitch[0]:
+                raise ValueError("batch_array: the R, G, B planes are not evenly spaced")
+            shape, strides = (3,) + shape, (step,) + strides
+        return DevicePlane(self, self.ptr + off, (len(self.sizes),) + shape, (lay.frame_bytes,) + strides, lay.dtype)
 
     def _download(self):
         from . import hip
@@ -554,7 +620,8 @@ class ReconContext:
         frame slots in device memory (p265r_batch_export) and return at once -> DeviceFrames.  ``dst`` None:
         the buffer is allocated here (hipMalloc) and owned by the result; an integer device address (with
         ``dst_bytes``): the caller's memory on this context's device, e.g. ``tensor.data_ptr()``.  The slots have
-        the tight (or ``pitch_align``) layout of the context's picture size."""
+        the tight (or ``pitch_align``) layout of the context's picture size -- or, with ``spec.size``, of that size
+        (p265r_batch_export_resized: every slot the same, whatever its picture's size)."""
         from . import hip
         lay = self.export_layout(spec)
         idx = list(range(len(batch.pics))) if only is None else [int(i) for i in only]
@@ -574,8 +641,14 @@ class ReconContext:
             raise ValueError("dst_bytes: the size of the caller's buffer")
         arr = (ctypes.c_int32 * len(idx))(*idx) if only is not None else None
         try:
-            _lib.check(self.lib.p265r_batch_export(self.handle, batch.handle, ctypes.byref(lay.desc), ctypes.c_void_p(int(dst)),
-                                                   int(dst_bytes), arr, len(idx)), "p265r_batch_export")
+            if lay.resize is not None:
+                _lib.check(self.lib.p265r_batch_export_resized(self.handle, batch.handle, ctypes.byref(lay.desc),
+                                                               ctypes.byref(lay.resize), ctypes.c_void_p(int(dst)),
+                                                               int(dst_bytes), arr, len(idx)), "p265r_batch_export_resized")
+            else:
+                _lib.check(self.lib.p265r_batch_export(self.handle, batch.handle, ctypes.byref(lay.desc),
+                                                       ctypes.c_void_p(int(dst)), int(dst_bytes), arr, len(idx)),
+                           "p265r_batch_export")
         except BaseException:
             if buf is not None:
                 buf.free()
