@@ -49,7 +49,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check tools/resize_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check tools/resize_check tools/prep_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -106,6 +106,14 @@ resize-check: tools/resize_check.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc
 		-o tools/resize_check tools/resize_check.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/export_host.cpp
 	./tools/resize_check
 .PHONY: resize-check
+
+# host check of job prep's short cuts (intra_prep.h prep_avail_clear, prep_filter_min_lg) against the generic
+# arithmetic, exhaustive: a stand-alone CPU program (hipcc, run without a GPU), not part of `all`
+PREP_CHECK ?= tools/prep_check
+prep-check: tools/prep_check.hip p265_amd/csrc/intra_prep.h p265_amd/csrc/intra.h p265_amd/csrc/tables.h include/p265r.h
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -o $(PREP_CHECK) tools/prep_check.hip
+	$(PREP_CHECK)
+.PHONY: prep-check
 
 # experiment builds: make variant V=name FLAGS="-DX=1"  ->  p265_amd/libp265r_name.so
 variant:

@@ -214,6 +214,44 @@ __device__ __forceinline__ IntraJob luma_job(const LumaJobLds& l, uint32_t zero_
 __device__ __forceinline__ uint32_t job_w1(uint32_t w0, uint32_t w5, uint32_t angv) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((w0 >> 17) & 63u) << 2), (int)angv) | ((w5 & kJ5Bit32) ? 1u << 21 : 0u);
 }
+// Availability of a TB's reference units in a CLEAR CTU: its left, top, top-left and top-right CTUs are all
+// usable (flags == 15) and it lies clear of the picture's right and bottom edges (x0 + 2 ctb <= w: no top
+// unit is cut, a TB's top-right units end at most one CTB beyond its CTU; y0 + ctb <= h: no bottom-left unit
+// is cut, the bottom-left units that z-order allows lie in the TB's own CTU).  Left, corner and top are then
+// always available, so the available units are ONE run from unit 0 (bottom-left available) or L / 2 up to unit
+// 2L (top-right available) or L + L / 2, never empty: ref_avail_mask32's mask and the fast path's run bounds
+// without the generic mask arithmetic.  Equal to them for every TB place (tools/prep_check.hip, exhaustive).
+struct PrepAvail {
+    uint32_t mlo, mhi;                                           // units 0..31, unit 32
+    bool full;                                                   // every unit available
+    int fa, la;                                                  // first / last available sample of the linear order
+};
+__host__ __device__ __forceinline__ PrepAvail prep_avail_clear(int c, int xr, int yr, int n, int ctb, uint32_t zw) {
+    const int sub = c ? 1 : 0;
+    const int xc = xr << sub, yc = yr << sub, nl = n << sub;      // luma, CTB-relative
+    const int L = nl >> 1, half = L >> 1;
+    const int xu = (xc >> 2) & 15;
+    const bool bl = (yc + nl < ctb) & ((xc == 0) | (((zw >> (2 * xu)) & 1u) != 0u));
+    const bool tr = xc + nl < ctb ? ((yc == 0) | (((zw >> (2 * xu + 1)) & 1u) != 0u)) : (yc == 0);
+    const int lo = bl ? 0 : half, hi = tr ? 2 * L : L + half;     // first and last available unit
+    PrepAvail a;
+    a.mlo = (hi >= 31 ? 0xffffffffu : (2u << hi) - 1u) & (0xffffffffu << lo);
+    a.mhi = hi == 32 ? 1u : 0u;
+    a.full = bl & tr;
+    a.fa = bl ? 0 : n;
+    a.la = tr ? 4 * n : 3 * n;
+    return a;
+}
+
+// The smallest log2 TB size at which the reference samples of intra mode m are filtered (8.4.4.2.3: not DC, and
+// min(|m - 26|, |m - 10|) > intraHorVerDistThres = 7, 1, 0 at 8x8, 16x16, 32x32, never at 4x4): the thresholds fall
+// with the size, so a mode filtered at one size is filtered at every larger one.  8 = never (DC, 10, 26).  The prep
+// wave holds it per lane (lane m = mode m) and picks it with a bpermute.  (tools/prep_check.hip compares with the rule.)
+__host__ __device__ __forceinline__ int prep_filter_min_lg(int m) {
+    const int da = m > 26 ? m - 26 : 26 - m, db = m > 10 ? m - 10 : 10 - m, d = da < db ? da : db;
+    return m == 1 ? 8 : (d > 7 ? 3 : (d > 1 ? 4 : (d > 0 ? 5 : 8)));
+}
+
 // grid (wc, hc, pictures), one 64-thread wave per CTU
 __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict__ pics, Geo g, BatchView v) {
     __shared__ LumaJobLds sj[kMaxCtuLuma];
@@ -231,6 +269,7 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
     const int lane = threadIdx.x;
     const uint32_t angv = lane < 35 ? c_angw[lane] : 0u;
     const uint32_t ztv = c_ztab[lane];                            // avail_ztab_word(lane >> 4, lane & 15)
+    const int filtv = prep_filter_min_lg(lane);                   // (lanes 0..34: a mode each)
     const int ctb = 1 << g.ctb_log2;
     const int x0 = cx << g.ctb_log2, y0 = cy << g.ctb_log2;
     // this CTU's record and its left / top / top-left / top-right neighbours' first 16 B (slice,
@@ -262,8 +301,8 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
         return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
     };
     // every TB record of the CTU is loaded up front, one 16-B load per lane and chunk, all in
-    // flight together (tb_count <= 384 at CTB 64, validate_picture); a TB's predecessor and
-    // successor come from the neighbouring lanes (DPP wave shifts, chunk edges by v_readlane)
+    // flight together (tb_count <= 384 at CTB 64, validate_picture), zeros beyond the last one; a
+    // TB's successor comes from the next lane (DPP wave shift, the chunk edge by v_readlane)
     uint4 rv[kPrepChunks];
     const uint4* tv = reinterpret_cast<const uint4*>(tbs);
 #pragma unroll
@@ -271,46 +310,47 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
         const int t = i * 64 + lane;
         rv[i] = t < cnt ? prep_ld16(tv + t) : make_uint4(0u, 0u, 0u, 0u);
     }
-    auto from_prev_lane = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); };
     auto from_next_lane = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false); };
     auto as_tb = [](uint4 v) { p265r_tb r; __builtin_memcpy(&r, &v, sizeof(r)); return r; };
+    // a clear CTU (prep_avail_clear): wave-uniform, decided once
+    const bool clear_ctu = ((uint32_t)__builtin_amdgcn_readfirstlane((int)flags) == 15u) & (x0 + 2 * ctb <= g.w) & (y0 + ctb <= g.h);
+    unsigned long long pn_prev = 0;                               // the previous chunk's Cb lanes that take their Cr
 #pragma unroll
     for (int ci = 0; ci < kPrepChunks; ++ci) {
         const int base = ci * 64;
         if (base >= cnt) break;                                   // wave-uniform
         const int t = base + lane;
         const bool valid = t < cnt;
-        const uint4 cv = rv[ci];
-        // words 0, 1 (position, size, component, mode, flags) of t - 1; words 0, 1, 3 of t + 1 --
-        // neighbouring lanes (DPP), across the chunk edges by v_readlane, selected without branches
-        const uint32_t pe_x = ci > 0 ? (uint32_t)__builtin_amdgcn_readlane((int)rv[ci > 0 ? ci - 1 : 0].x, 63) : 0u;
-        const uint32_t pe_y = ci > 0 ? (uint32_t)__builtin_amdgcn_readlane((int)rv[ci > 0 ? ci - 1 : 0].y, 63) : 0u;
+        const uint4 cv = rv[ci];                                  // (all zero beyond the CTU's last record)
+        // words 0, 1, 3 (position; size, component, mode, flags; coef_off) of t + 1: the next lane (DPP),
+        // across the chunk edge by v_readlane, selected without branches.  Beyond the last record they are
+        // zero, as the records were loaded
         const int cn = ci + 1 < kPrepChunks ? ci + 1 : ci;
         const uint32_t ne_x = ci + 1 < kPrepChunks ? (uint32_t)__builtin_amdgcn_readlane((int)rv[cn].x, 0) : 0u;
         const uint32_t ne_y = ci + 1 < kPrepChunks ? (uint32_t)__builtin_amdgcn_readlane((int)rv[cn].y, 0) : 0u;
         const uint32_t ne_w = ci + 1 < kPrepChunks ? (uint32_t)__builtin_amdgcn_readlane((int)rv[cn].w, 0) : 0u;
-        const bool has_prev = valid & (t > 0), has_next = valid & (t + 1 < cnt);
         // the DPP moves are pinned here (empty asm): left to the compiler they sink into divergent
         // branches of their selects, each with its own exec-mask save / restore
-        uint32_t dp0 = from_prev_lane(cv.x), dp1 = from_prev_lane(cv.y);
         uint32_t dn0 = from_next_lane(cv.x), dn1 = from_next_lane(cv.y), dn3 = from_next_lane(cv.w);
-        asm volatile("" : "+v"(dp0), "+v"(dp1), "+v"(dn0), "+v"(dn1), "+v"(dn3));
-        const uint32_t p0 = has_prev ? (lane == 0 ? pe_x : dp0) : 0u;
-        const uint32_t p1 = has_prev ? (lane == 0 ? pe_y : dp1) : 0u;
+        asm volatile("" : "+v"(dn0), "+v"(dn1), "+v"(dn3));
         const uint4 nv = make_uint4(lane == 63 ? ne_x : dn0, lane == 63 ? ne_y : dn1, 0u, lane == 63 ? ne_w : dn3);
-        p265r_tb rec = as_tb(valid ? cv : make_uint4(0u, 0u, 0u, 0u));
-        p265r_tb next = as_tb(has_next ? nv : make_uint4(0u, 0u, 0u, 0u));
+        const p265r_tb rec = as_tb(cv), next = as_tb(nv);
         // tb_same_tu_chroma on the raw words: word 0 = x | y << 16, word 1 = log2 | c_idx << 8 |
-        // pred_mode << 16 | flags << 24 (Cb then Cr of one TU: same position, size, mode, PCM flag)
+        // pred_mode << 16 | flags << 24 (Cb then Cr of one TU: same position, size, mode, PCM flag); false
+        // for an all-zero record on either side (c_idx 0)
         auto same_tu = [](uint32_t cb0, uint32_t cb1, uint32_t cr0, uint32_t cr1) {   // (bitwise: no short circuit)
             return (cb0 == cr0) & ((cb1 & 0xff00u) == 0x0100u) & ((cr1 & 0xff00u) == 0x0200u) &
                    (((cb1 ^ cr1) & (0x00ff00ffu | (uint32_t)P265R_TB_PCM << 24)) == 0u);
         };
-        const bool cr_taken = has_prev & same_tu(p0, p1, cv.x, cv.y);
-        const bool keep = valid & !cr_taken;
-        const bool pair_next = has_next & same_tu(cv.x, cv.y, nv.x, nv.y);
-        const bool kl = keep && rec.c_idx == 0;
-        const unsigned long long ml = __ballot(kl), mc = __ballot(keep && !kl);
+        // one test per record: a Cb whose next record is its Cr.  That Cr is the lane after it (lane 0: the
+        // previous chunk's lane 63), so the taken Cr records are the ballot shifted by one -- scalar work
+        const bool pair_next = same_tu(cv.x, cv.y, nv.x, nv.y);
+        const unsigned long long pn = __ballot(pair_next);
+        const unsigned long long taken = pn << 1 | pn_prev >> 63;
+        pn_prev = pn;
+        const bool kl = valid & (rec.c_idx == 0);                 // (a luma record is never taken)
+        const unsigned long long ml = __ballot(kl), mc = __ballot(valid & (rec.c_idx != 0)) & ~taken;
+        const bool keep = kl | (((uint32_t)(mc >> lane) & 1u) != 0u);
         const int slot = kl ? out_l + rank(ml) : out_c + rank(mc);
         out_l += __popcll(ml);
         out_c += __popcll(mc);
@@ -329,13 +369,31 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
             // z-order word of the TB's size and unit row (ztv: lane i holds avail_ztab_word word i)
             const int zs = (31 - __clz(n)) + sub - 2, yu = (yr << sub) >> 2;
             const uint32_t zw = (uint32_t)__builtin_amdgcn_ds_bpermute((zs * 16 + yu) << 2, (int)ztv);
-            uint32_t mhi;
-            const uint32_t mlo = ref_avail_mask32(c, xr, yr, n, x0, y0, g.w, g.h, ctb, flags, zw, mhi);
-            const uint32_t full_lo = L == 16 ? 0xffffffffu : (1u << (2 * L + 1)) - 1u;
-            const bool m_full = (mlo == full_lo) & (mhi == (L == 16 ? 1u : 0u)), m_none = (mlo | mhi) == 0u;
+            // (mask; all / none / one run of units available; the run's sample bounds [fa, la] of the fast path)
+            uint32_t mlo, mhi;
+            bool m_full, m_none, contig;
+            int fa, la;
+            if (clear_ctu) {                                      // (uniform)
+                const PrepAvail a = prep_avail_clear(c, xr, yr, n, ctb, zw);
+                mlo = a.mlo; mhi = a.mhi; m_full = a.full; m_none = false; contig = true; fa = a.fa; la = a.la;
+            } else {
+                mlo = ref_avail_mask32(c, xr, yr, n, x0, y0, g.w, g.h, ctb, flags, zw, mhi);
+                const uint32_t full_lo = L == 16 ? 0xffffffffu : (1u << (2 * L + 1)) - 1u;
+                m_full = (mlo == full_lo) & (mhi == (L == 16 ? 1u : 0u));
+                m_none = (mlo | mhi) == 0u;
+                // one contiguous run of available units [ulo, uhi] -> sample bounds [fa, la]
+                const int US = c ? 1 : 2;
+                const int ulo = mlo ? __ffs((int)mlo) - 1 : 32;
+                const int uhi = mhi ? 32 : 31 - __clz((int)(mlo | 1u));
+                // the available units form one run [ulo, uhi] (32-bit pieces; mhi = unit 32)
+                const uint32_t lo_cut = ulo >= 32 ? 0u : (0xffffffffu << ulo);
+                contig = mlo == (mhi ? lo_cut : (lo_cut & (uhi >= 31 ? 0xffffffffu : ((2u << uhi) - 1u))));
+                fa = ulo < L ? (ulo << US) : (ulo == L ? 2 * n : 2 * n + 1 + ((ulo - L - 1) << US));
+                la = uhi < L ? ((uhi + 1) << US) - 1 : (uhi == L ? 2 * n : 2 * n + ((uhi - L) << US));
+            }
             // ---- filtering decision (8.4.4.2.3), luma only in 4:2:0 ---------------------------
-            const int dist = min(abs(mode - 26), abs(mode - 10));
-            const bool fon = (c == 0) & (n != 4) & (mode != 1) & (dist > (n == 8 ? 7 : (n == 16 ? 1 : 0)));
+            // (min(|mode - 26|, |mode - 10|) > intraHorVerDistThres, never DC: the mode's smallest filtered size)
+            const bool fon = (c == 0) & (lg >= __builtin_amdgcn_ds_bpermute(mode << 2, filtv));
             const uint32_t filt = fon ? ((n == 32 && g.strong) ? 2u : 1u) : 0u;
             const uint32_t f0 = rec.flags;
             const uint32_t f1 = pair ? next.flags : 0u;
@@ -353,16 +411,8 @@ __global__ __launch_bounds__(64) void intra_prep_kernel(const DevPic* __restrict
                                 ((f0 & P265R_TB_PCM) ? J_PCM : 0u) | filt << 24 | raw(fh0) << 26 | raw(fh1) << 27 |
                                 coded(fh0) << 28 | coded(fh1) << 29 | (m_full ? J_ALL : 0u) | (m_none ? J_NONE : 0u);
             const uint32_t w2 = mlo;
-            // fast path: one contiguous run of available units [ulo, uhi] -> sample bounds [fa, la]
+            // fast path: the available units are one run (or none), its sample bounds [fa, la]
             const bool fast_size = ((c == 0) & (n <= 16)) | ((cm == 3u) & (n <= (g.quad & 4 ? 4 : 8)));
-            const int US = c ? 1 : 2;
-            const int ulo = mlo ? __ffs((int)mlo) - 1 : 32;
-            const int uhi = mhi ? 32 : 31 - __clz((int)(mlo | 1u));
-            // the available units form one run [ulo, uhi] (32-bit pieces; mhi = unit 32)
-            const uint32_t lo_cut = ulo >= 32 ? 0u : (0xffffffffu << ulo);
-            const bool contig = mlo == (mhi ? lo_cut : (lo_cut & (uhi >= 31 ? 0xffffffffu : ((2u << uhi) - 1u))));
-            const int fa = ulo < L ? (ulo << US) : (ulo == L ? 2 * n : 2 * n + 1 + ((ulo - L - 1) << US));
-            const int la = uhi < L ? ((uhi + 1) << US) - 1 : (uhi == L ? 2 * n : 2 * n + ((uhi - L) << US));
             const bool fast = fast_size & !(f0 & P265R_TB_PCM) & (m_none | contig);
             const uint32_t w5 = !fast ? 0u : (m_none ? J5_FAST : (J5_FAST | (uint32_t)fa | (uint32_t)la << 8));
             const uint32_t w5s = w5 | (mhi ? kJ5Bit32 : 0u);
