@@ -36,6 +36,20 @@
  *                   batch takes | "steps" | "none") with "last_launch_row_waves"
  * chroma_format_idc 2 and 3 are P265R_EINVAL from p265r_create.
  *
+ * Unequal bit depths (BitDepthY != BitDepthC, Main 10 / RExt) are opt-in: p265r_params.split_bit_depth = 1.
+ *   p265r_create    with the flag, bit_depth_luma and bit_depth_chroma are each 8..12 on their own; without it
+ *                   unequal depths stay P265R_EUNSUPPORTED.  A value above 1 is P265R_EINVAL.  Monochrome ignores
+ *                   the flag with the chroma depth; the flag with equal depths changes nothing.
+ *   device planes   the context is WIDE when either depth exceeds 8: all three planes are then uint16_t in device
+ *                   memory, whatever their own depth
+ *   p265r_picture   out[c] / recon[c] (P265R_PIC_RECON_INPUT too) are typed per component: uint8_t for a component
+ *                   of 8 bits, little-endian uint16_t above.  The 8-bit component of a wide context is narrowed on
+ *                   the device before the download and widened on the host during the upload.
+ *   p265r_batch_digest*     a wide context digests every plane in its 16-bit device form (an 8-bit component as
+ *                           uint16_t samples: W/2 words of 2 samples per row)
+ *   p265r_batch_export*     P265R_EINVAL (from the layout functions too);  p265r_batch_hash_async: P265R_EUNSUPPORTED
+ *   p265r_describe  "bit_depth" (luma) and "bit_depth_chroma"
+ *
  * Conventions: every function returns int (0 = P265R_OK, < 0 = error code, see
  * p265r_strerror); no exception or C++ type crosses this boundary.  All host
  * buffers are owned by the caller.  A context is bound to one device and is not
@@ -92,7 +106,8 @@ typedef struct p265r_params {
     uint16_t pic_height;              /* pic_height_in_luma_samples               */
     uint8_t  chroma_format_idc;       /* 1 (4:2:0) or 0 (4:0:0, monochrome)       */
     uint8_t  bit_depth_luma;          /* BitDepthY: 8, or 9..12 (uint16_t planes)   */
-    uint8_t  bit_depth_chroma;        /* BitDepthC: equal to bit_depth_luma (monochrome: ignored) */
+    uint8_t  bit_depth_chroma;        /* BitDepthC: equal to bit_depth_luma unless split_bit_depth
+                                         (monochrome: ignored)                      */
     uint8_t  ctb_log2_size;           /* CtbLog2SizeY, 4..6                       */
     uint8_t  min_tb_log2_size;        /* MinTbLog2SizeY, 2..5                     */
     uint8_t  max_tb_log2_size;        /* MaxTbLog2SizeY, <= 5                     */
@@ -105,7 +120,9 @@ typedef struct p265r_params {
                                          scaling.py:32-44)                          */
     int8_t   pps_cb_qp_offset;        /* cQpPicOffset of Cb chroma deblocking (8.7.2.5.5) */
     int8_t   pps_cr_qp_offset;        /* cQpPicOffset of Cr chroma deblocking     */
-    uint8_t  reserved[11];
+    uint8_t  split_bit_depth;         /* 1: bit_depth_luma and bit_depth_chroma may differ, each 8..12;
+                                         0: unequal depths are P265R_EUNSUPPORTED; > 1: P265R_EINVAL */
+    uint8_t  reserved[10];
 } p265r_params;
 
 /* One CTU, raster order, PicSizeInCtbsY per picture.  32 bytes. */
@@ -151,8 +168,8 @@ typedef struct p265r_picture {
                                  1 = deblocking and SAO leave the block's samples untouched
                                  (pcm_loop_filter_disabled && pcm, or cu_transquant_bypass)   */
     void*            out[3];  /* decoded (post-deblocking, post-SAO) planes Y, Cb, Cr; stride =
-                                 plane width in samples; uint8_t samples at BitDepth 8, uint16_t
-                                 at 9..12.  NULL = do not download                              */
+                                 plane width in samples; per component uint8_t samples at BitDepth
+                                 8, uint16_t at 9..12.  NULL = do not download                  */
     void*            recon[3];/* optional in-loop-filter input (reconstruction before deblocking
                                  and SAO), same layout; NULL = skip.  Written by download, or
                                  read by upload with P265R_PIC_RECON_INPUT                     */
@@ -236,8 +253,10 @@ int  p265r_batch_status(p265r_ctx* ctx, p265r_batch* batch);
  * in-loop filters.  out[3 * i + c] = sum over the 4-sample words of plane c of picture i (row y,
  * word k; the picture's own width W, W/4 words per row) of mix64(word | (y * W/4 + k) << 32)
  * mod 2^64, mix64 = the splitmix64 finalizer (p265_amd/digest.py restates it on the host);
- * n = 3 * the batch's pictures.  Returns what p265r_batch_status returns afterwards.  Lets a
- * benchmark check every picture it timed.  No counterpart in the reference. */
+ * n = 3 * the batch's pictures.  16-bit planes: words of 2 samples, W/2 per row -- in a wide context
+ * (split_bit_depth) that holds for every plane, an 8-bit component included: the digest is of the
+ * 16-bit device form (digest.plane_digest(..., wide=True)).  Returns what p265r_batch_status returns
+ * afterwards.  Lets a benchmark check every picture it timed.  No counterpart in the reference. */
 int  p265r_batch_digest(p265r_ctx* ctx, p265r_batch* batch, int which, uint64_t* out, int n);
 /* The same digest ENQUEUED on the batch's lane after every run enqueued so far, into slot `slot`
  * (0 .. P265R_DIGEST_SLOTS-1) of the batch's digest buffer; returns without waiting (the buffer is

@@ -47,7 +47,8 @@ class Params(ctypes.Structure):
                 ("strong_intra_smoothing", ctypes.c_uint8), ("constrained_intra_pred", ctypes.c_uint8),
                 ("sample_adaptive_offset", ctypes.c_uint8), ("loop_filter_across_tiles", ctypes.c_uint8),
                 ("scaling_list_enabled", ctypes.c_uint8), ("pps_cb_qp_offset", ctypes.c_int8),
-                ("pps_cr_qp_offset", ctypes.c_int8), ("reserved", ctypes.c_uint8 * 11)]
+                ("pps_cr_qp_offset", ctypes.c_int8), ("split_bit_depth", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 10)]
 
 
 class PictureC(ctypes.Structure):

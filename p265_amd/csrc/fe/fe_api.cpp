@@ -359,6 +359,8 @@ void fill_info(const PictureJob& j, const PictureRecords& r, p265fe_picture_info
     pr.scaling_list_enabled = (uint8_t)s.scaling_list_enabled;
     pr.pps_cb_qp_offset = (int8_t)(mono ? 0 : p.cb_qp_offset);
     pr.pps_cr_qp_offset = (int8_t)(mono ? 0 : p.cr_qp_offset);
+    // BitDepthY != BitDepthC: the back-end takes the two depths only with its opt-in flag
+    pr.split_bit_depth = (uint8_t)((!mono && s.bit_depth_c != s.bit_depth_y) ? 1 : 0);
     out->ctus = r.ctus.data();
     out->n_ctus = (uint32_t)r.ctus.size();
     out->tbs = r.tbs.data();

@@ -176,8 +176,9 @@ __host__ __device__ __forceinline__ uint32_t ref_avail_mask32(int c, int xr, int
     return (bl ? m_bl : 0u) | (left ? m_l : 0u) | (corner ? m_c : 0u) | (top ? m_t : 0u) | (tr ? m_tr : 0u);
 }
 
-// One launch per anti-diagonal step (P265R_SCHEDULE=steps; the only schedule of the 16-bit sample path,
-// Main 10: T = uint16_t, planes of Geo::stride samples of 2 bytes).
+// One launch per anti-diagonal step (P265R_SCHEDULE=steps).  The row pipeline (intra_rows.h) is the default
+// schedule at every bit depth; of the 16-bit sample path (T = uint16_t, planes of Geo::stride samples of 2
+// bytes) this kernel is the fallback for pictures too wide for the row kernel's LDS (p265r_create).
 template <typename T>
 __global__ __launch_bounds__(64) void intra_step_kernel(const DevPic* __restrict__ pics,
                                                        const int16_t* __restrict__ pool,

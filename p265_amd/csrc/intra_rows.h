@@ -92,7 +92,7 @@ typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 __device__ __forceinline__ lds_u8* lds8(uint32_t a) { return (lds_u8*)(uintptr_t)a; }
 __device__ __forceinline__ lds_u32* lds32(uint32_t a) { return (lds_u32*)(uintptr_t)a; }
-// sample T (uint8_t, uint16_t for BitDepth 9..10, int16_t for 11..12) at SAMPLE address s (byte address s * sizeof(T)): the
+// sample T (uint8_t; a wide context: uint16_t for BitDepthC <= 10, int16_t for 11..12) at SAMPLE address s (byte address s * sizeof(T)): the
 // job functions compute their LDS addresses in sample units, so one formula serves both sample sizes
 template <typename T>
 __device__ __forceinline__ __attribute__((address_space(3))) T* ldsT(uint32_t s) {
@@ -113,7 +113,7 @@ __device__ __forceinline__ uint32_t pmul(uint32_t w, uint32_t packed) {
     }
 }
 
-// Packed angular interpolation ((32 - f) a + f b + 16) >> 5 of a Cb | Cr pair (wa + wb = 32).  BitDepth 11-12
+// Packed angular interpolation ((32 - f) a + f b + 16) >> 5 of a Cb | Cr pair (wa + wb = 32).  BitDepthC 11-12
 // (sample type int16_t, the row kernel's tag for them) passes 16 bits per half (32 x 4095), so each sample is
 // split into 6-bit halves a = 64 ah + al: the result is 2 (wa ah + wb bh) + ((wa al + wb bl + 16) >> 5)
 // exactly (64 X is a multiple of 32), every partial sum below 2^12 per half.
@@ -184,7 +184,8 @@ __device__ __forceinline__ uint32_t angtab_entry(int m, int p) {
     return a | b << 8 | (uint32_t)fact << 16 | (uint32_t)(32 - fact) << 24;
 }
 
-template <typename T>            // sample type: uint8_t (BitDepth 8), uint16_t (9..10), int16_t (11..12: a tag, pang)
+template <typename T>            // sample type: uint8_t (BitDepth 8); 16-bit samples: uint16_t (BitDepthC <= 10), int16_t
+                                 // (BitDepthC 11..12: a tag, pang -- the CHROMA depth picks it, luma never reads it)
 struct WaveLdsT {                // one wave's private CTU state (4564 B at 8 bits): a wave holds one row
     T        ref[2][136];        // unit at a time, luma OR chroma, so their areas overlap
     union {                      // ref: raw / final linear reference arrays
@@ -955,7 +956,9 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
     WaveLdsT<T>& L = reinterpret_cast<WaveLdsT<T>*>(smem + 256 + prog_bytes)[wave];
     const int line_bytes = g.w + 2 * g.cw;            // Y | Cb | Cr bottom sample rows (samples)
     T* lines = reinterpret_cast<T*>(smem + 256 + prog_bytes + W * sizeof(WaveLdsT<T>));
-    const int maxv = (1 << g.bd[0]) - 1;              // BitDepth: luma = chroma (p265r_create)
+    // BitDepthY and BitDepthC may differ (p265r_params.split_bit_depth): one clip limit per component, chosen at
+    // compile time by each job call site below (a luma site passes maxv_y, a chroma site maxv_c)
+    const int maxv_y = (1 << g.bd[0]) - 1, maxv_c = (1 << g.bd[1]) - 1;
 
     uint32_t* const atab = reinterpret_cast<uint32_t*>(lines + (size_t)fs_count * 2 * line_bytes);   // AngTab4
     if (threadIdx.x == 0) {
@@ -1336,29 +1339,29 @@ void intra_rows_kernel(const DevPic* __restrict__ pics,
                 const T* tlp = reinterpret_cast<const T*>(lds_ptr(tl));
                 const T* tcp = reinterpret_cast<const T*>(lds_ptr(tc));
                 // (8 bits: the constant 255 folds into every job function, as before the 16-bit path)
-                const int mv = PB == 1 ? 255 : maxv;
+                const int mvy = PB == 1 ? 255 : maxv_y, mvc = PB == 1 ? 255 : maxv_c;
                 if (w5 & J5_QUAD) {
-                    if ((w0 >> 15) & 3u) recon_quad<true, T>(lbase, tcb, cr_off, w0, w1, w2, tab, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, mv);
-                    else recon_quad<false, T>(lbase, tl, 0u, w0, w1, w2, tab, c16, ln, mv);
+                    if ((w0 >> 15) & 3u) recon_quad<true, T>(lbase, tcb, cr_off, w0, w1, w2, tab, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, mvc);
+                    else recon_quad<false, T>(lbase, tl, 0u, w0, w1, w2, tab, c16, ln, mvy);
                 } else if (w5 & J5_FAST) {
                     switch (sel) {
-                        case 0: recon_fast<2, false, T>(lbase, tl, w0, w1, w5, c16, ln, tab, mv); break;
-                        case 1: recon_fast<3, false, T>(lbase, tl, w0, w1, w5, c16, ln, tab, mv); break;
-                        case 2: recon_fast16<T>(lbase, tl, w0, w1, w5, make_uint4((uint32_t)c16, (uint32_t)c16m, 0u, 0u), ln, mv); break;
-                        case 5: recon_cfast8<T>(lbase, tcb, cr_off, w0, w1, w5, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, tab, mv); break;
-                        default: recon_fast<2, true, T>(lbase, tc, w0, w1, w5, c16, ln, tab, mv); break;
+                        case 0: recon_fast<2, false, T>(lbase, tl, w0, w1, w5, c16, ln, tab, mvy); break;
+                        case 1: recon_fast<3, false, T>(lbase, tl, w0, w1, w5, c16, ln, tab, mvy); break;
+                        case 2: recon_fast16<T>(lbase, tl, w0, w1, w5, make_uint4((uint32_t)c16, (uint32_t)c16m, 0u, 0u), ln, mvy); break;
+                        case 5: recon_cfast8<T>(lbase, tcb, cr_off, w0, w1, w5, (int)((uint32_t)c16 | (uint32_t)c16m << 16), ln, tab, mvc); break;
+                        default: recon_fast<2, true, T>(lbase, tc, w0, w1, w5, c16, ln, tab, mvc); break;
                     }
                 } else {
                   const uint4* ra_p = res_addr(w0, w3, w4);
                   const uint4 ca = ld16(ra_p), cb = ld16(ra_p + 1);
                   switch (sel) {
-                    case 0: recon_job<2, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mv); break;
-                    case 1: recon_job<3, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mv); break;
-                    case 2: recon_job<4, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mv); break;
-                    case 3: recon_job<5, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mv); break;
-                    case 4: recon_job<2, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mv); break;
-                    case 5: recon_job<3, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mv); break;
-                    default: recon_job<4, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mv); break;
+                    case 0: recon_job<2, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mvy); break;
+                    case 1: recon_job<3, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mvy); break;
+                    case 2: recon_job<4, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mvy); break;
+                    case 3: recon_job<5, false, T>(LL, tlp, w0, w1, w2, ca, cb, ln, mvy); break;
+                    case 4: recon_job<2, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mvc); break;
+                    case 5: recon_job<3, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mvc); break;
+                    default: recon_job<4, true, T>(LL, tcp, w0, w1, w2, ca, cb, ln, mvc); break;
                   }
                 }
                 P265R_MARK("job_end");

@@ -30,6 +30,7 @@
 #include "intra_rows.h"
 #include "loopfilter.h"
 #include "loopfilter16.h"
+#include "narrow.h"
 #include "pichash.h"
 #include "sao16.h"
 #include "residual.h"
@@ -188,6 +189,11 @@ struct p265r_batch {
     unsigned long long* d_dig = nullptr;   // p265r_batch_digest_async slots: P265R_DIGEST_SLOTS x n_pics x 3
     uint8_t* d_hash = nullptr;         // p265r_batch_hash_async: 16 bytes per plane (the SEI form), then one 32-bit
                                        // accumulator per plane (checksum, CRC)
+    // p265r_batch_download in a wide context with an 8-bit component (narrow.h): the staging area of the narrowed
+    // planes, its items in front (allocated at the first such download, grown when a later one asks for more)
+    unsigned char* d_narrow = nullptr;
+    size_t narrow_bytes = 0;
+    std::vector<NarrowItem> narrow_items;   // (host copy: lives until the batch is freed, the H2D copy reads it)
     hipEvent_t intra_done = nullptr;   // recorded after each run's intra phase (the last reader of the
                                        // residual pool and job lists): the next run's residual + prep
                                        // phase waits for it instead of for the whole previous run
@@ -334,7 +340,8 @@ int launch_rows(p265r_ctx* ctx, p265r_batch* b, hipStream_t st, bool alone) {
         // the per-diagonal schedule for pictures too wide for W = 8)
         int w = ctx->row_waves ? ctx->row_waves : (alone ? 12 : 8);
         if (w == 12 && rows_lds_bytes<uint16_t>(ctx->geo, 12, 2) > 160 * 1024) w = 8;
-        if (ctx->geo.bd[0] > 10)                    // BitDepth 11..12: int16_t tags the split angular sums (pang)
+        if (ctx->geo.bd[1] > 10)                    // BitDepthC 11..12: int16_t tags the split angular sums (pang) of
+                                                    // the Cb | Cr pairs; the luma jobs never read the tag
             return w == 12 ? launch_rows_w<12, 1, false, false, int16_t>(ctx, b, st, alone)
                            : launch_rows_w<8, 1, false, false, int16_t>(ctx, b, st, alone);
         return w == 12 ? launch_rows_w<12, 1, false, false, uint16_t>(ctx, b, st, alone)
@@ -549,12 +556,15 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     *out = nullptr;
     const p265r_params& p = *params;
     if (!params_ok(p)) return P265R_EINVAL;
-    // BitDepth 8 (uint8_t planes) or 9..12 with one depth for luma and chroma (uint16_t planes; 13..14 would
-    // need SaoOffsetVal beyond the int8 of the CTU record)
-    // (monochrome, chroma_format_idc 0: bit_depth_chroma, the chroma QP offsets and a scaling table's chroma
-    // entries mean nothing and are ignored)
+    // BitDepth 8 (uint8_t planes) or 9..12 (uint16_t planes; 13..14 would need SaoOffsetVal beyond the int8 of the
+    // CTU record), one depth for luma and chroma unless split_bit_depth allows two
+    // (monochrome, chroma_format_idc 0: bit_depth_chroma, split_bit_depth, the chroma QP offsets and a scaling
+    // table's chroma entries mean nothing and are ignored)
     const bool mono = p.chroma_format_idc == 0;
-    if (p.bit_depth_luma < 8 || p.bit_depth_luma > 12 || (!mono && p.bit_depth_chroma != p.bit_depth_luma) || p.scaling_list_enabled > 1)
+    if (!mono && p.split_bit_depth > 1) return P265R_EINVAL;
+    const bool split_bd = !mono && p.split_bit_depth == 1;
+    if (p.bit_depth_luma < 8 || p.bit_depth_luma > 12 || p.scaling_list_enabled > 1) return P265R_EUNSUPPORTED;
+    if (!mono && (split_bd ? (p.bit_depth_chroma < 8 || p.bit_depth_chroma > 12) : p.bit_depth_chroma != p.bit_depth_luma))
         return P265R_EUNSUPPORTED;
     const int n = p265r_device_count();
     if (n < 0) return n;
@@ -577,7 +587,8 @@ int p265r_create(int device, const p265r_params* params, p265r_ctx** out) {
     g.wc = (g.w + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
     g.hc = (g.h + (1 << g.ctb_log2) - 1) >> g.ctb_log2;
     g.bd[0] = p.bit_depth_luma; g.bd[1] = g.bd[2] = ctx->params.bit_depth_chroma;
-    g.pel16 = p.bit_depth_luma > 8 ? 1 : 0;
+    // wide context: either depth above 8 puts uint16_t samples in all three planes (one sample type per kernel)
+    g.pel16 = (g.bd[0] > 8 || g.bd[1] > 8) ? 1 : 0;
     g.strong = p.strong_intra_smoothing;
     g.lf_tiles = p.loop_filter_across_tiles;
     g.nf_w = (g.w + 7) / 8;
@@ -850,10 +861,18 @@ int upload_batch(p265r_ctx* ctx, const p265r_picture* pics, const p265r_sparse_c
     if (e == hipSuccess && plan.recon_input) {
         const Geo& g = ctx->geo;
         const size_t pb = plan.pel_bytes;
+        // (a wide context's 8-bit component: its uint8_t planes are widened into the staging buffer first)
+        if (!plan.wide_at.empty())
+            parallel_for(n_pics, [&](int i) {
+                for (int c = 0; c < (g.mono ? 1 : 3); ++c)
+                    if (plan.wide_at[i][c] != SIZE_MAX) widen_plane(plan, i, c, pics, host);
+            });
         for (int i = 0; i < n_pics && e == hipSuccess; ++i)
             for (int c = 0; c < (g.mono ? 1 : 3) && e == hipSuccess; ++c) {
                 const size_t wd = (size_t)(plan.psize[i][0] >> (c ? 1 : 0)), ht = (size_t)(plan.psize[i][1] >> (c ? 1 : 0));
-                e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, pics[i].recon[c], wd * pb, wd * pb, ht, hipMemcpyHostToDevice, st);
+                const bool wide = !plan.wide_at.empty() && plan.wide_at[i][c] != SIZE_MAX;
+                const void* src = wide ? static_cast<const void*>(host + plan.wide_at[i][c]) : pics[i].recon[c];
+                e = hipMemcpy2DAsync(b->h_pics[i].rec[c], g.stride[c] * pb, src, wd * pb, wd * pb, ht, hipMemcpyHostToDevice, st);
                 b->h2d_bytes += wd * pb * ht;
             }
     }
@@ -1130,16 +1149,58 @@ int p265r_batch_download(p265r_ctx* ctx, p265r_batch* b, const p265r_picture* pi
     // planes to copy: (host destination, device source, row pitch, width, height)
     struct Item { void* dst; const unsigned char* src; int pitch, w, h; size_t bytes; };
     std::vector<Item> items;
-    const int pb = g.pel16 ? 2 : 1;                          // bytes per sample
+    const int pb = g.pel16 ? 2 : 1;                          // bytes per sample on the device
+    // a wide context's 8-bit component (unequal bit depths): the host planes are uint8_t, so the requested planes
+    // are narrowed on the device first (narrow.h) and copied from the batch's staging area, rows tight
+    b->narrow_items.clear();
+    std::vector<size_t> narrow_of, narrow_off;               // per narrow item: its copy item, its offset in the area
+    size_t narrow_need = 0;
+    int nw_max = 0, nh_max = 0;
     for (int i = 0; i < n_pics; ++i)
         for (int c = 0; c < (g.mono ? 1 : 3); ++c) {      // (monochrome: out[1..2] / recon[1..2] are never touched)
             const int sub = c ? 1 : 0;
-            const int w = (b->size[i][0] >> sub) * pb, h = b->size[i][1] >> sub;     // (w in bytes)
+            const bool narrow = g.pel16 && g.bd[c] <= 8;
+            const int ws = b->size[i][0] >> sub, h = b->size[i][1] >> sub;
+            const int w = ws * (narrow ? 1 : pb);                                    // (w in bytes)
             const int pitch = (c ? g.stride[1] : g.stride[0]) * pb;
-            if (pics[i].out[c]) items.push_back({pics[i].out[c], b->h_pics[i].out[c], pitch, w, h, (size_t)w * h});
-            if (pics[i].recon[c] && !b->recon_input)
-                items.push_back({pics[i].recon[c], b->h_pics[i].rec[c], pitch, w, h, (size_t)w * h});
+            auto add = [&](void* dst, const uint8_t* src) {
+                if (narrow) {
+                    narrow_of.push_back(items.size());
+                    b->narrow_items.push_back({reinterpret_cast<const uint16_t*>(src), nullptr, ws, h, c ? g.stride[1] : g.stride[0],
+                                               0});
+                    narrow_off.push_back(narrow_need);
+                    narrow_need += align_up((size_t)w * h, 256);
+                    nw_max = std::max(nw_max, ws);
+                    nh_max = std::max(nh_max, h);
+                }
+                items.push_back({dst, src, narrow ? w : pitch, w, h, (size_t)w * h});
+            };
+            if (pics[i].out[c]) add(pics[i].out[c], b->h_pics[i].out[c]);
+            if (pics[i].recon[c] && !b->recon_input) add(pics[i].recon[c], b->h_pics[i].rec[c]);
         }
+    if (!b->narrow_items.empty()) {
+        const size_t n_it = b->narrow_items.size();
+        const size_t head = align_up(sizeof(NarrowItem) * n_it, 256);
+        const int segs = (nw_max + kNarrowSeg - 1) / kNarrowSeg;
+        if ((unsigned long long)n_it * (unsigned)segs >= (1ull << 31)) return P265R_ERANGE;
+        if (b->narrow_bytes < head + narrow_need) {          // (an earlier download's launch may still read the old one)
+            if (b->d_narrow) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_narrow); }
+            b->d_narrow = nullptr;
+            b->narrow_bytes = 0;
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->d_narrow), head + narrow_need);
+            if (e != hipSuccess) { b->d_narrow = nullptr; return e == hipErrorOutOfMemory ? P265R_ENOMEM : hip_fail(e, "hipMalloc"); }
+            b->narrow_bytes = head + narrow_need;
+        }
+        for (size_t k = 0; k < n_it; ++k) {
+            NarrowItem& it = b->narrow_items[k];
+            it.dst = b->d_narrow + head + narrow_off[k];
+            items[narrow_of[k]].src = it.dst;
+        }
+        HIP_TRY(hipMemcpyAsync(b->d_narrow, b->narrow_items.data(), sizeof(NarrowItem) * n_it, hipMemcpyHostToDevice, b->stream));
+        narrow_kernel<<<dim3((unsigned)(n_it * segs), (unsigned)((nh_max + kNarrowWaves - 1) / kNarrowWaves)), 64 * kNarrowWaves, 0,
+                        b->stream>>>(reinterpret_cast<const NarrowItem*>(b->d_narrow), segs);
+        HIP_TRY(hipGetLastError());
+    }
     // D2H through two halves of a pinned bounce buffer (DMA at pinned speed; the copy into the
     // caller's pageable planes runs on host threads while the next chunk's DMA is in flight)
     if (!ctx->dl_stage) {
@@ -1263,6 +1324,8 @@ int p265r_batch_digest_slots(p265r_ctx* ctx, p265r_batch* b, uint64_t* out, int 
 int p265r_batch_hash_async(p265r_ctx* ctx, p265r_batch* b, int hash_type) {
     if (!ctx || !b) return P265R_EINVAL;
     if (hash_type != P265R_HASH_MD5 && hash_type != P265R_HASH_CRC && hash_type != P265R_HASH_CHECKSUM) return P265R_EINVAL;
+    // unequal bit depths: D.3.19 hashes each plane in its own sample width, the device planes have one (host hashing)
+    if (ctx->geo.bd[0] != ctx->geo.bd[1]) return P265R_EUNSUPPORTED;
     if (b->runs == 0) return P265R_ESTATE;                  // (no output planes yet, as for p265r_batch_export)
     HIP_TRY(hipSetDevice(ctx->device));
     const int n_planes = 3 * b->n_pics;
@@ -1320,6 +1383,7 @@ int p265r_batch_export(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* 
     if (n <= 0 || n > b->n_pics || n > 65535) return P265R_EINVAL;
     // ---- host checks: nothing is launched unless all of them pass ----------------------------
     const int B = ctx->params.bit_depth_luma;
+    if (ctx->geo.bd[0] != ctx->geo.bd[1]) return P265R_EINVAL;      // unequal bit depths: as p265r_export_layout
     ExportShape shape;
     if (const int rc = export_check_desc(*desc, B, &shape, ctx->geo.mono != 0)) return rc;
     std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
@@ -1386,6 +1450,7 @@ int p265r_batch_export_resized(p265r_ctx* ctx, p265r_batch* b, const p265r_expor
     if (n <= 0 || n > b->n_pics || n > 65535) return P265R_EINVAL;
     // ---- host checks: nothing is launched unless all of them pass ----------------------------
     const int B = ctx->params.bit_depth_luma;
+    if (ctx->geo.bd[0] != ctx->geo.bd[1]) return P265R_EINVAL;      // unequal bit depths: as p265r_resize_layout
     ExportShape shape;
     if (const int rc = resize_check_desc(*desc, *rs, B, ctx->geo.mono != 0, &shape)) return rc;
     uint64_t slot_bytes = 0;
@@ -1456,6 +1521,7 @@ int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (b->intra_done) (void)hipEventDestroy(b->intra_done);
     if (b->d_dig) (void)hipFree(b->d_dig);
     if (b->d_hash) (void)hipFree(b->d_hash);
+    if (b->d_narrow) (void)hipFree(b->d_narrow);
     for (void* p : b->exp_idx) (void)hipFree(p);
     if (b->mem) {
         // keep the larger of (cache, this allocation) for the next upload (its runs are complete)
@@ -1533,7 +1599,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
         "\"fair\": %d, \"quad\": %d, \"luma_lead\": %d, \"sao_rows\": %d, \"skip\": %d, \"debug_sync\": %d, "
         "\"pipeline\": %d, \"fork_prep\": %d, \"pipe_waves\": %d, \"hw_queues\": \"%s\", \"num_cus\": %d, \"diag_build\": %d, "
         "\"experiments_build\": %d, \"split\": %d, \"last_launch_split\": %d, \"xg\": %d, \"last_launch_xg\": %d, "
-        "\"phase_order\": %d, \"early_residual\": %d, \"bit_depth\": %d, \"row_launches\": {\"w12\": %lld, \"w8\": %lld, \"w16_split\": %lld, \"xg\": %lld, \"other\": %lld}, "
+        "\"phase_order\": %d, \"early_residual\": %d, \"bit_depth\": %d, \"bit_depth_chroma\": %d, \"row_launches\": {\"w12\": %lld, \"w8\": %lld, \"w16_split\": %lld, \"xg\": %lld, \"other\": %lld}, "
         "\"sparse_expand\": \"%s\", \"sparse_expand_stream\": %d, \"last_sparse_expand_ms\": %.4f, "
         "\"chroma_format_idc\": %d, \"last_launch_layout\": \"%s\", \"last_launch_row_waves\": %d, "
         "\"env_overrides\": [%s]}",
@@ -1558,7 +1624,7 @@ int p265r_describe(p265r_ctx* ctx, char* buf, int size) {
         0,
 #endif
         0, ctx->split, ctx->last_split ? 1 : 0, ctx->xg, ctx->last_xg ? 1 : 0, P265R_PHASE_ORDER, P265R_EARLY_RESIDUAL,
-        (int)ctx->params.bit_depth_luma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], 0ll,
+        (int)ctx->params.bit_depth_luma, (int)ctx->params.bit_depth_chroma, ctx->row_launches[0], ctx->row_launches[1], ctx->row_launches[2], ctx->row_launches[3], 0ll,
         "lds tile", 0, ctx->last_expand_ms,
         (int)ctx->params.chroma_format_idc, ctx->last_layout, ctx->last_row_waves,
         ctx->describe.c_str());

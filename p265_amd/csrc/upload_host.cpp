@@ -3,6 +3,7 @@
 // tools/upload_check.cpp).
 #include "upload_host.h"
 
+#include <cstdint>
 #include <cstring>
 
 #include "sparse_host.h"
@@ -260,6 +261,20 @@ int plan_upload(const p265r_params& p, const Geo& g, int n_ctus, int xg, bool sp
         u.ent_kc.push_back(ef);
         u.beg_kc.push_back(bf);
     }
+    // recon input in a wide context: the planes of an 8-bit component go up as uint16_t, widened into the staging
+    // buffer behind everything else
+    if (u.recon_input && g.pel16 && (g.bd[0] <= 8 || (!g.mono && g.bd[1] <= 8))) {
+        u.s_wide = align_up(u.stage_need, 256);
+        u.wide_at.assign(n_pics, {SIZE_MAX, SIZE_MAX, SIZE_MAX});
+        size_t wf = u.s_wide;
+        for (int i = 0; i < n_pics; ++i)
+            for (int c = 0; c < (g.mono ? 1 : 3); ++c) {
+                if (g.bd[c] > 8) continue;
+                u.wide_at[i][c] = wf;
+                wf = align_up(wf + sizeof(uint16_t) * (size_t)(u.psize[i][0] >> (c ? 1 : 0)) * (size_t)(u.psize[i][1] >> (c ? 1 : 0)), 256);
+            }
+        u.stage_need = wf;
+    }
     return P265R_OK;
 }
 
@@ -363,6 +378,13 @@ void pack_picture(const UploadPlan& u, int i, const p265r_picture* pics, const p
     } else {
         dp.nofilter = nullptr;
     }
+}
+
+void widen_plane(const UploadPlan& u, int i, int c, const p265r_picture* pics, unsigned char* stage) {
+    const size_t n = (size_t)(u.psize[i][0] >> (c ? 1 : 0)) * (size_t)(u.psize[i][1] >> (c ? 1 : 0));
+    const uint8_t* src = static_cast<const uint8_t*>(pics[i].recon[c]);
+    uint16_t* dst = reinterpret_cast<uint16_t*>(stage + u.wide_at[i][c]);
+    for (size_t k = 0; k < n; ++k) dst[k] = src[k];
 }
 
 void close_chunk(const UploadPlan& u, int k, unsigned char* stage) {

@@ -94,6 +94,11 @@ struct UploadPlan {
     // closes the last)
     std::vector<std::array<size_t, RC_NUM>> ent_at, beg_at;
     std::vector<size_t> ent_kc, beg_kc;
+    // recon-input planes of an 8-bit component in a wide context (unequal bit depths: every device plane is
+    // uint16_t): widened into the staging buffer behind everything else (s_wide; wide_at[i][c]: plane c of
+    // picture i, tight rows of its own width, SIZE_MAX: the plane is copied from the caller's memory as it is)
+    size_t s_wide = 0;
+    std::vector<std::array<size_t, 3>> wide_at;
 
     // Chunk k's copies, to enqueue once its pictures are packed: its ranges of the CTU and TB records, of each
     // class slab of the coefficient pool, of each residual job list and of the no-filter maps; sparse: its
@@ -121,6 +126,9 @@ void pack_picture(const UploadPlan& plan, int i, const p265r_picture* pics, cons
 // sparse, after chunk k's pictures are packed: each class range's closing begin word (the index past its
 // last entry)
 void close_chunk(const UploadPlan& plan, int k, unsigned char* stage);
+// recon-input plane c of picture i, uint8_t samples at the caller's, as uint16_t into its staging range
+// (UploadPlan::wide_at, which is not SIZE_MAX)
+void widen_plane(const UploadPlan& plan, int i, int c, const p265r_picture* pics, unsigned char* stage);
 // [0, o_ctus) of the staging buffer: the DevPic table, then zeros (alignment, error word, row-kernel slots)
 void pack_header(const UploadPlan& plan, const DevPic* dev_pics, unsigned char* stage);
 

@@ -13,7 +13,9 @@ on the GPU instead of on downloaded planes.  A monochrome (4:0:0) stream writes 
 ``--mono-output i420`` appends chroma planes of 1 << (BitDepth - 1), and the GPU formats take their one-plane
 forms (nv12 / p010: a grey CbCr plane; RGB: R = G = B).  ``--resize WxH`` (with ``--resize-filter nearest|bilinear|
 area``) scales every frame of a GPU format to that size on the GPU (the scaled device-side output); the default
-``i420`` host path does not scale and refuses both.
+``i420`` host path does not scale and refuses both.  A stream whose luma and chroma bit depths differ takes the
+``i420`` host path with ``--hash-on host`` only (the GPU formats and the GPU hash refuse it by name); when either
+depth exceeds 8 its file holds every plane as 16-bit little-endian samples, values unscaled.
 """
 import argparse
 import sys

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import bitstream
 from . import recon
+from . import records as R
 
 
 @dataclass
@@ -42,6 +43,16 @@ class DecodedFrame:
                                  # (its batch's buffer is freed when the last frame of the batch is released or
                                  # collected); planes is then None unless the picture hashes were verified on the host
     bit_depth: int = 8           # BitDepthY of the stream (the grey of a monochrome picture's missing chroma)
+    bit_depth_chroma: int = 8    # BitDepthC (monochrome: BitDepthY); where it differs from bit_depth the planes are
+                                 # typed per component: uint8 for a component of 8 bits, uint16 above
+
+    def file_planes(self):
+        """cropped() as a raw video file holds it: one sample width per file, so when any plane has 16-bit samples
+        every plane is written as 16-bit little-endian, values unscaled (as HM writes unequal bit depths)."""
+        planes = self.cropped()
+        if any(p.dtype.itemsize > 1 for p in planes):
+            planes = [p.astype("<u2", copy=False) for p in planes]
+        return planes
 
     def cropped(self):
         l, r, t, b = self.crop
@@ -195,7 +206,9 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
     ``hash_on``: "host" (default) hashes the downloaded planes on the host pool; "device" computes the picture
     hashes of every batch on the GPU behind its run (ReconContext.hash_async; batches are also cut where the
     SEI's hash type changes), reads 48 bytes per picture and never hashes on the host: with ``export`` no
-    plane leaves the device.  ``hash_ok`` and HashMismatch mean the same in both."""
+    plane leaves the device.  ``hash_ok`` and HashMismatch mean the same in both.
+    A stream whose luma and chroma bit depths differ decodes with host hashing and host output only: ``export``
+    or ``hash_on="device"`` on it raises ValueError (records.require_equal_depths)."""
     import time
     if hash_on not in ("host", "device"):
         raise ValueError("hash_on: 'host' or 'device', not %r" % (hash_on,))
@@ -256,6 +269,10 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
         return ls
 
     def submit(group):
+        if export is not None:
+            R.require_equal_depths(group[0].params, "decoder: export= (device-side output)")
+        if device_hash:
+            R.require_equal_depths(group[0].params, "decoder: hash_on='device' (device-side picture hash)")
         lane = lanes_for(group[0].params, group[0].scaling)[k_submit[0] % depth]
         k_submit[0] += 1
         slots.acquire()                 # at most `depth` batches between upload and download
@@ -343,7 +360,8 @@ def decode_chunks(chunks: Iterable[bytes], device: int = 0, batch: int = DEFAULT
             fr = DecodedFrame(poc=d.poc, output_rank=-1, decode_index=int(d.picture.meta["decode_index"]),
                               planes=planes, crop=tuple(int(v) for v in d.crop), hash_ok=None,
                               device=frames.slot(k) if frames is not None else None,
-                              bit_depth=int(d.params["bit_depth_luma"]))
+                              bit_depth=int(d.params["bit_depth_luma"]),
+                              bit_depth_chroma=int(d.params["bit_depth_luma" if R.is_mono(d.params) else "bit_depth_chroma"]))
             futs = None
             if hashes is not None:
                 nb = len(d.hash[0])
@@ -438,7 +456,8 @@ def grey_chroma(fr: DecodedFrame):
 
 
 def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CHUNK, mono_output: str = "y", **kw) -> dict:
-    """Stream a bitstream file to a cropped I420 YUV file in output order; returns counts.  With ``export=`` the
+    """Stream a bitstream file to a cropped I420 YUV file in output order (one sample width per file:
+    DecodedFrame.file_planes); returns counts.  With ``export=`` the
     file holds the exported frames instead (one device-to-host copy per batch, no host crop or interleave).
     A monochrome (4:0:0) stream writes luma-only frames; ``mono_output="i420"`` appends grey chroma planes
     (grey_chroma) on the host path."""
@@ -455,7 +474,7 @@ def decode_file(path: str, output: Optional[str] = None, chunk: int = DEFAULT_CH
             if f and fr.device is not None:
                 f.write(fr.device.tobytes())
             elif f:
-                planes = fr.cropped()
+                planes = fr.file_planes()
                 if len(planes) == 1 and mono_output == "i420":
                     planes = planes + grey_chroma(fr)
                 for p in planes:
@@ -472,5 +491,5 @@ def write_yuv(frames: List[DecodedFrame], path: str):
     """Planar 4:2:0 YUV (I420), cropped, in output order; the frames of a monochrome stream: Y only."""
     with open(path, "wb") as f:
         for fr in frames:
-            for p in fr.cropped():
+            for p in fr.file_planes():
                 f.write(np.ascontiguousarray(p).tobytes())

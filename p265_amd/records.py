@@ -30,7 +30,7 @@ PARAMS_DTYPE = np.dtype([
     ("strong_intra_smoothing", "u1"), ("constrained_intra_pred", "u1"),
     ("sample_adaptive_offset", "u1"), ("loop_filter_across_tiles", "u1"),
     ("scaling_list_enabled", "u1"), ("pps_cb_qp_offset", "i1"), ("pps_cr_qp_offset", "i1"),
-    ("reserved", "u1", 11)])
+    ("split_bit_depth", "u1"), ("reserved", "u1", 10)])
 assert PARAMS_DTYPE.itemsize == 32
 
 CTU_DTYPE = np.dtype([
@@ -52,7 +52,8 @@ def make_params(**kw) -> np.ndarray:
     d = dict(pic_width=352, pic_height=288, chroma_format_idc=1, bit_depth_luma=8,
              bit_depth_chroma=8, ctb_log2_size=6, min_tb_log2_size=2, max_tb_log2_size=5,
              strong_intra_smoothing=1, constrained_intra_pred=0, sample_adaptive_offset=1,
-             loop_filter_across_tiles=1, scaling_list_enabled=0, pps_cb_qp_offset=0, pps_cr_qp_offset=0)
+             loop_filter_across_tiles=1, scaling_list_enabled=0, pps_cb_qp_offset=0, pps_cr_qp_offset=0,
+             split_bit_depth=0)
     for k, v in kw.items():
         if k not in d:
             raise KeyError("unknown params field %r" % k)
@@ -75,10 +76,42 @@ def n_planes(params) -> int:
 
 
 def require_420(params, what):
-    """The tile, halo and multi-rank paths handle three planes: monochrome params are refused by name."""
+    """The tile, halo and multi-rank paths handle three planes of one sample type: monochrome params and params
+    with unequal bit depths are refused by name."""
     if is_mono(params):
         raise ValueError("%s: monochrome (chroma_format_idc 0) pictures are not supported here; decode them as "
                          "whole pictures (recon.ReconContext, decoder.decode_*)" % what)
+    require_equal_depths(params, what)
+
+
+def split_depths(params) -> bool:
+    """BitDepthY != BitDepthC (4:2:0 params; a monochrome picture has no chroma depth)."""
+    return not is_mono(params) and int(params["bit_depth_luma"]) != int(params["bit_depth_chroma"])
+
+
+def require_equal_depths(params, what):
+    """The tile, halo and multi-rank paths, the device-side output and the device-side picture hash take one bit
+    depth per picture: params with BitDepthY != BitDepthC are refused by name."""
+    if split_depths(params):
+        raise ValueError("%s: unequal bit depths (BitDepthY %d, BitDepthC %d) are not supported here; decode such "
+                         "pictures whole (recon.ReconContext, decoder.decode_*) with host hashing and host output"
+                         % (what, int(params["bit_depth_luma"]), int(params["bit_depth_chroma"])))
+
+
+def check_depths(params):
+    """The bit-depth rules of p265r_create: each depth 8..12; unequal depths only with split_bit_depth = 1 (a value
+    above 1 is invalid).  Monochrome params: the luma depth alone."""
+    y, c, f = int(params["bit_depth_luma"]), int(params["bit_depth_chroma"]), int(params["split_bit_depth"])
+    if not 8 <= y <= 12:
+        raise RecordError("bit_depth_luma %d outside 8..12" % y)
+    if is_mono(params):
+        return
+    if f > 1:
+        raise RecordError("split_bit_depth is 0 or 1, got %d" % f)
+    if f == 0 and y != c:
+        raise RecordError("bit depths %d / %d differ without split_bit_depth" % (y, c))
+    if not 8 <= c <= 12:
+        raise RecordError("bit_depth_chroma %d outside 8..12" % c)
 
 
 def plane_dtypes(params):
@@ -291,6 +324,7 @@ def validate(params, pic: Picture):
     what keeps a malformed record from faulting the GPU.
     """
     params = pic_params(params, pic)
+    check_depths(params)
     wc, hc = ctb_grid(params)
     if pic.ctus.dtype != CTU_DTYPE or pic.tbs.dtype != TB_DTYPE or pic.coef.dtype != np.int16:
         raise RecordError("record dtypes do not match the ABI")

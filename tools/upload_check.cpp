@@ -638,9 +638,68 @@ static void rejections() {
     }
 }
 
+// ---- recon input at unequal bit depths: the 8-bit component goes up widened -------------------------------
+// A wide context (p265r_params.split_bit_depth) keeps every device plane as uint16_t: the planner places each
+// uint8_t recon-input plane's widened copy behind the rest of the staging buffer, widen_plane fills it.
+static void wide_recon_input() {
+    static const int depths[3][2] = {{8, 10}, {10, 8}, {10, 10}};
+    for (const auto& d : depths) {
+        g_case = d[0] == 8 ? "recon input (8, 10)" : d[1] == 8 ? "recon input (10, 8)" : "recon input (10, 10)";
+        Ctx cx = make_ctx(72, 40, 4, 10, true);
+        cx.p.bit_depth_luma = (uint8_t)d[0]; cx.p.bit_depth_chroma = (uint8_t)d[1];
+        cx.p.split_bit_depth = d[0] != d[1];
+        cx.g.bd[0] = d[0]; cx.g.bd[1] = cx.g.bd[2] = d[1];
+        static const int sz[2][2] = {{72, 40}, {40, 24}};
+        Batch b;
+        std::vector<std::vector<uint8_t>> planes;                 // exact-size host planes, in the component's type
+        const Ctx gen = make_ctx(72, 40, 4, 8, true);             // (records legal at either depth: qp <= 51)
+        for (int i = 0; i < 2; ++i) b.pics.push_back(make_pic(gen, PicOpt{sz[i][0], sz[i][1], false, false, NONE_CODED, false}, 8100 + i));
+        for (int i = 0; i < 2; ++i)
+            for (int c = 0; c < 3; ++c) {
+                const size_t n = (size_t)(sz[i][0] >> (c ? 1 : 0)) * (sz[i][1] >> (c ? 1 : 0));
+                std::vector<uint8_t> v(n * (cx.g.bd[c] > 8 ? 2 : 1));
+                for (size_t k = 0; k < v.size(); ++k) v[k] = (uint8_t)(37 * k + 11 * c + i);
+                exact(v);
+                planes.push_back(v);
+            }
+        for (int i = 0; i < 2; ++i) {
+            b.pics[i].flags = P265R_PIC_RECON_INPUT;
+            for (int c = 0; c < 3; ++c) b.pics[i].recon[c] = planes[3 * i + c].data();
+        }
+        UploadPlan base, u;
+        if (plan_of(cx, b, false, &u) != P265R_OK) { EXPECT(!"plan of a recon-input batch"); continue; }
+        EXPECT(u.recon_input && u.ragged && u.pel_bytes == 2);
+        if (d[0] == d[1]) { EXPECT(u.wide_at.empty() && u.s_wide == 0); continue; }
+        for (auto& pic : b.pics) pic.flags = 0;                   // the same batch without the recon input
+        EXPECT(plan_of(cx, b, false, &base) == P265R_OK);
+        for (auto& pic : b.pics) pic.flags = P265R_PIC_RECON_INPUT;
+        EXPECT(u.s_wide == align_up(base.stage_need, 256) && u.total == base.total && u.wide_at.size() == 2);
+        std::vector<unsigned char> stage(u.stage_need, 0xEE);
+        exact(stage);
+        const auto pv = b.views(false);
+        size_t end = u.s_wide;
+        for (int i = 0; i < 2; ++i)
+            for (int c = 0; c < 3; ++c) {
+                const size_t n = (size_t)(sz[i][0] >> (c ? 1 : 0)) * (sz[i][1] >> (c ? 1 : 0));
+                if (cx.g.bd[c] > 8) { EXPECT(u.wide_at[i][c] == SIZE_MAX); continue; }
+                EXPECT(u.wide_at[i][c] == end && end % 256 == 0);
+                widen_plane(u, i, c, pv.data(), stage.data());
+                const uint16_t* w = reinterpret_cast<const uint16_t*>(stage.data() + u.wide_at[i][c]);
+                bool same = true;
+                for (size_t k = 0; k < n; ++k) same = same && w[k] == planes[3 * i + c][k];
+                EXPECT(same);
+                end = align_up(end + 2 * n, 256);
+            }
+        EXPECT(end == u.stage_need);
+        for (size_t k = 0; k < u.s_wide; ++k)
+            if (stage[k] != 0xEE) { EXPECT(!"widen_plane wrote in front of its range"); break; }
+    }
+}
+
 int main() {
     good_batches();
     rejections();
+    wide_recon_input();
     if (g_fail) { std::printf("upload_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("upload_check ok\n");
     return 0;
