@@ -418,6 +418,53 @@ int  p265r_batch_export_resized(p265r_ctx* ctx, p265r_batch* batch, const p265r_
                                 const p265r_resize_desc* rs, void* dev_dst, uint64_t dst_bytes,
                                 const int32_t* pic_index, int n);
 
+/* ---- grid export: rows x cols pictures of a batch as ONE frame, cut to a window, turned and mirrored -----------
+ * No counterpart in the reference.  What a HEIF `grid` item with `irot` / `imir` asks for (p265_amd/heif.py).
+ *   Canvas.  All listed pictures have the same own size tw x th.  The canvas is cols tw x rows th luma samples; its
+ *     luma sample (x, y) is sample (x % tw, y % th) of tile (y / th) * cols + x / tw; chroma the same at half sizes.
+ *   Window.  [crop_left, out_width - crop_right) x [crop_top, out_height - crop_bottom) of the canvas, W x H.
+ *   Frame F.  Exactly what p265r_batch_export would write if the canvas were one decoded picture of that size and
+ *     the window its crop: sample types, the MSB16 shift, the CbCr interleave, the integer RGB conversion and the
+ *     float scale carry over unchanged.  In particular the P265R_UP_BILINEAR chroma taps are clamped to the CANVAS
+ *     (not to a tile, not to out_width x out_height) and cross tile seams.
+ *   Orientation.  orientation = k | m << 2: the destination holds F turned k = 0..3 quarter turns ANTICLOCKWISE,
+ *     then, with m = 1, mirrored left-right: numpy's np.rot90(F, k), then [:, ::-1].  Every plane is transformed
+ *     alike; a CbCr pair or an RGB triple moves as one element.  Chroma is NOT re-sited after a turn: a chroma
+ *     plane is turned as the array it is, so the half-sample offset of chroma_sample_loc_type 0 turns with it.
+ *     With k odd the destination frame is H x W luma samples (planes of H/2 x W/2 chroma likewise), and
+ *     p265r_grid_layout lays out that frame.
+ *   Sources.  A monochrome context takes the monochrome rules of p265r_batch_export (Y; grey CbCr; R = G = B).
+ *     rows = cols = 1 with orientation 0 is byte-identical to p265r_batch_export with the crop the window implies. */
+typedef struct p265r_grid_desc {
+    uint32_t rows, cols;            /* 1..256 each; rows * cols pictures per frame, row-major      */
+    uint32_t out_width, out_height; /* the grid item's output size in luma samples                 */
+    uint32_t orientation;           /* k | m << 2: k = 0..3 quarter turns ANTICLOCKWISE, then m = 1
+                                       mirrors left-right.  Restated: np.rot90(F, k), then [:, ::-1] */
+    uint32_t reserved[3];           /* 0, else P265R_EINVAL */
+} p265r_grid_desc;
+
+/* host only, no context: like p265r_export_layout, for the frame a grid of tile_width x tile_height pictures gives
+ * under desc's format / sample / crop and grid's size and orientation; validates both (the P265R_EINVAL list of
+ * p265r_batch_export_grid that needs no batch).  A canvas above 65535 samples on an axis is P265R_EINVAL. */
+int  p265r_grid_layout(const p265r_params* params, int tile_width, int tile_height, const p265r_grid_desc* grid,
+                       p265r_export_desc* desc, uint32_t pitch_align);
+/* as p265r_batch_export: enqueued on the batch's lane behind its runs, no stream of its own, returns without
+ * waiting, every check on the host before a launch.  ONE kernel launch for k even; for k odd two (the frame is
+ * written untransposed into a staging area, then transposed through LDS), the staging allocated once per batch and
+ * reused (grown only when a later call needs more).  pic_index lists rows * cols pictures per frame: tile
+ * r * cols + c of frame f at f * rows * cols + r * cols + c; NULL = the batch in order (n_frames * rows * cols must
+ * then equal the batch's pictures).  Every frame shares desc and grid.  P265R_EINVAL, on top of everything
+ * p265r_batch_export refuses (desc's layout is checked against the ORIENTED frame): rows or cols 0 or above 256, an
+ * orientation above 7, a reserved word set; listed pictures of differing own sizes; out_width outside
+ * ((cols - 1) tw, cols tw] or out_height outside ((rows - 1) th, rows th]; an empty window; an odd window width or
+ * height with a YUV format of a 4:2:0 source (odd is legal for RGB, and for a monochrome planar source); an odd
+ * crop_left / crop_top on a 4:2:0 source (crop_right / crop_bottom only need to leave a legal window); a picture
+ * listed twice; n_frames * rows * cols above 65535.  P265R_EUNSUPPORTED for a split_bit_depth context of unequal
+ * depths. */
+int  p265r_batch_export_grid(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
+                             const p265r_grid_desc* grid, void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index,
+                             int n_frames);
+
 /* ---- device-side picture hash: the decoded_picture_hash SEI values (D.3.19) computed in device memory ----
  * No counterpart in the reference (no SEI support, nalu.py:130-131).  The hash of a plane runs over its
  * pictureData: the samples of the picture's OWN size (uncropped) in raster order, one byte per sample at

@@ -110,6 +110,8 @@ class DecodedPicture:
     max_num_reorder: int = 0    # sps_max_num_reorder_pics of its SPS (output bumping, C.5.2.2)
     output_flag: bool = True    # PicOutputFlag
     scaling: Optional[np.ndarray] = None   # the 2032-byte intra ScalingFactor table (scaling_list_enabled)
+    colour: Optional[tuple] = None  # the SPS VUI's video_signal_type: (matrix_coeffs, video_full_range_flag) -- matrix
+                                    # 2 (unspecified) when it sends no colour description; None: no video_signal_type
 
 
 class _Owner:
@@ -196,6 +198,14 @@ def _fail(lib, h, n, what):
     raise cls("%s: %s (%d)" % (what, msg, n))
 
 
+def colour_of(reserved):
+    """p265fe_picture_info.reserved -> (matrix_coeffs, full_range) or None: bit 15 = video_signal_type present, bit 8 =
+    video_full_range_flag, bits 0-7 = matrix_coeffs (0 when the stream has no VUI colour information)."""
+    if not reserved & 0x8000:
+        return None
+    return (reserved & 0xFF, bool(reserved & 0x100))
+
+
 def _collect(get, n, owner, validate, base=0):
     out = []
     info = PictureInfoC()
@@ -226,7 +236,7 @@ def _collect(get, n, owner, validate, base=0):
                                   nal_unit_type=int(info.nal_unit_type), n_slices=int(info.n_slices),
                                   n_cus=int(info.n_cus), hash_type=int(info.hash_type), hash=hv,
                                   cvs_id=int(info.cvs_id), max_num_reorder=int(info.max_num_reorder),
-                                  output_flag=bool(info.output_flag),
+                                  output_flag=bool(info.output_flag), colour=colour_of(int(info.reserved)),
                                   scaling=(np.ctypeslib.as_array(ctypes.cast(info.scaling_factors, ctypes.POINTER(ctypes.c_uint8)),
                                                                  (2032,)).copy() if info.scaling_factors else None)))
     return out

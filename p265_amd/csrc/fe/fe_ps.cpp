@@ -236,14 +236,20 @@ static void parse_hrd(BitReader& br, int common, int max_sub_layers_minus1) {
 }
 
 // vui_parameters() (E.2.1); the reference stops here (sps.py:131 calls an undefined object)
-static void parse_vui(BitReader& br, int max_sub_layers_minus1) {
+static void parse_vui(BitReader& br, int max_sub_layers_minus1, Sps& sps) {
     if (br.flag()) {                       // aspect_ratio_info_present_flag
         if (br.u(8) == 255) br.skip(32);   // sar_width, sar_height
     }
     if (br.flag()) br.skip(1);             // overscan
     if (br.flag()) {                       // video_signal_type_present_flag
-        br.skip(3 + 1);
-        if (br.flag()) br.skip(24);
+        br.skip(3);                        // video_format
+        const int full = br.flag() ? 1 : 0;    // video_full_range_flag
+        int matrix = 2;                    // matrix_coeffs when no colour description is sent: unspecified (E.3.1)
+        if (br.flag()) {                   // colour_description_present_flag
+            br.skip(16);                   // colour_primaries, transfer_characteristics
+            matrix = (int)br.u(8);
+        }
+        sps.colour_info = 0x8000 | full << 8 | matrix;
     }
     if (br.flag()) { br.ue(); br.ue(); }   // chroma_loc_info
     br.skip(3);                            // neutral_chroma, field_seq, frame_field_info
@@ -335,7 +341,7 @@ Sps parse_sps(BitReader& br) {
     }
     s.temporal_mvp = br.flag();
     s.strong_intra_smoothing = br.flag();
-    if (br.flag()) parse_vui(br, s.max_sub_layers_minus1);
+    if (br.flag()) parse_vui(br, s.max_sub_layers_minus1, s);
     if (br.flag()) {                                  // sps_extension_present_flag
         int range = br.flag();
         br.skip(3);                                   // multilayer, 3d, scc

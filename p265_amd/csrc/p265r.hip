@@ -25,6 +25,8 @@
 #include "export_host.h"
 #include "resize.h"
 #include "resize_host.h"
+#include "grid.h"
+#include "grid_host.h"
 #include "intra.h"
 #include "intra_prep.h"
 #include "intra_rows.h"
@@ -186,6 +188,8 @@ struct p265r_batch {
     int runs = 0;              // p265r_batch_run calls so far
     std::vector<void*> exp_idx;        // p265r_batch_export: device copies of the pic_index lists of the exports
                                        // enqueued since the lane was last synchronised (p265r_batch_status)
+    void* grid_stage = nullptr;        // p265r_batch_export_grid, quarter turns: the untransposed frames (allocated at the
+    size_t grid_stage_bytes = 0;       // first such call and reused; grown when a later call needs more)
     unsigned long long* d_dig = nullptr;   // p265r_batch_digest_async slots: P265R_DIGEST_SLOTS x n_pics x 3
     uint8_t* d_hash = nullptr;         // p265r_batch_hash_async: 16 bytes per plane (the SEI form), then one 32-bit
                                        // accumulator per plane (checksum, CRC)
@@ -517,6 +521,59 @@ int launch_resize(const p265r_export_desc& d, uint32_t filter, const DevPic* d_p
             default: rgb(std::enable_if<true, S>{}); break;                       // NATIVE
         }
     }
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// Pass 1 of p265r_batch_export_grid on stream st: n frames of the a.W x a.H window.
+template <typename S>
+int launch_grid(const p265r_export_desc& d, const Geo& g, const GridArgs& a, int n, hipStream_t st) {
+    const auto grid = [&](int group, int row_units) {
+        return dim3((unsigned)((a.W / group + 2 + kExportLanes - 1) / kExportLanes),
+                    (unsigned)((row_units + kExportRows - 1) / kExportRows), (unsigned)n);
+    };
+    if (d.format == P265R_FMT_PLANAR) {
+        grid_yuv_kernel<S, false><<<grid(16 / (int)sizeof(S), g.mono ? a.H : 2 * a.H), 256, 0, st>>>(g, a);
+    } else if (d.format == P265R_FMT_SEMIPLANAR) {
+        grid_yuv_kernel<S, true><<<grid(16 / (int)sizeof(S), a.H + a.H / 2), 256, 0, st>>>(g, a);
+    } else {
+        const bool bil = d.upsample == P265R_UP_BILINEAR && !g.mono;    // (a monochrome source has nothing to upsample)
+        const int pairs = bil ? a.H / 2 + 1 : (a.H + 1) / 2;
+        auto rgb = [&](auto dtag, auto packed, auto bl) {
+            using D = typename decltype(dtag)::type;
+            constexpr bool PK = decltype(packed)::value, BL = decltype(bl)::value;
+            grid_rgb_kernel<S, D, PK, BL><<<grid(sizeof(D) == 1 ? 16 : 8, pairs), 256, 0, st>>>(g, a);
+        };
+        auto by_shape = [&](auto dtag) {
+            const bool pk = d.format == P265R_FMT_RGB_PACKED;
+            if (pk && bil) rgb(dtag, std::true_type{}, std::true_type{});
+            else if (pk) rgb(dtag, std::true_type{}, std::false_type{});
+            else if (bil) rgb(dtag, std::false_type{}, std::true_type{});
+            else rgb(dtag, std::false_type{}, std::false_type{});
+        };
+        switch (d.sample) {
+            case P265R_SMP_U8: by_shape(std::enable_if<true, uint8_t>{}); break;
+            case P265R_SMP_F16: by_shape(std::enable_if<true, _Float16>{}); break;
+            case P265R_SMP_F32: by_shape(std::enable_if<true, float>{}); break;
+            default: by_shape(std::enable_if<true, S>{}); break;                  // NATIVE
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// Pass 2 (quarter turns): every plane of n staged frames transposed into the destination.
+int launch_grid_transpose(const p265r_export_desc& d, int es, const GridTransposeArgs& a, int n_planes, int n, hipStream_t st) {
+    const dim3 grid((unsigned)((a.w[0] + kGridTile - 1) / kGridTile), (unsigned)(n_planes * a.tiles_y), (unsigned)n);
+    auto go = [&](auto utag) {
+        using U = typename decltype(utag)::type;
+        if (d.format == P265R_FMT_RGB_PACKED) grid_transpose_kernel<U, 3, 3><<<grid, 256, 0, st>>>(a);
+        else if (d.format == P265R_FMT_SEMIPLANAR) grid_transpose_kernel<U, 1, 2><<<grid, 256, 0, st>>>(a);
+        else grid_transpose_kernel<U, 1, 1><<<grid, 256, 0, st>>>(a);
+    };
+    if (es == 1) go(std::enable_if<true, uint8_t>{});
+    else if (es == 2) go(std::enable_if<true, uint16_t>{});
+    else go(std::enable_if<true, uint32_t>{});
     HIP_TRY(hipGetLastError());
     return P265R_OK;
 }
@@ -1511,6 +1568,115 @@ int p265r_batch_export_resized(p265r_ctx* ctx, p265r_batch* b, const p265r_expor
     return P265R_OK;
 }
 
+int p265r_batch_export_grid(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* desc, const p265r_grid_desc* gd,
+                            void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index, int n_frames) {
+    if (!ctx || !b || !desc || !gd || !dev_dst) return P265R_EINVAL;
+    // ---- host checks: nothing is launched unless all of them pass ----------------------------
+    if (gd->rows < 1 || gd->rows > 256 || gd->cols < 1 || gd->cols > 256) return P265R_EINVAL;
+    const int tiles = (int)(gd->rows * gd->cols);
+    // (NULL = the batch in order: n_frames must then account for every picture of it)
+    if (!pic_index && (n_frames <= 0 || (int64_t)n_frames * tiles != b->n_pics)) return P265R_EINVAL;
+    if (n_frames <= 0 || (int64_t)n_frames * tiles > 65535 || (int64_t)n_frames * tiles > b->n_pics) return P265R_EINVAL;
+    const int n = n_frames * tiles;
+    const int B = ctx->params.bit_depth_luma;
+    if (ctx->geo.bd[0] != ctx->geo.bd[1]) return P265R_EUNSUPPORTED;   // unequal bit depths
+    std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
+    int tw = 0, th = 0;
+    for (int i = 0; i < n; ++i) {
+        const int pic = pic_index ? pic_index[i] : i;
+        if (pic < 0 || pic >= b->n_pics) return P265R_EINVAL;
+        if (pic_index) {
+            if (seen[(size_t)pic]) return P265R_EINVAL;
+            seen[(size_t)pic] = 1;
+        }
+        if (i == 0) { tw = b->size[(size_t)pic][0]; th = b->size[(size_t)pic][1]; }
+        else if (b->size[(size_t)pic][0] != tw || b->size[(size_t)pic][1] != th) return P265R_EINVAL;
+    }
+    GridShape gs;
+    if (const int rc = grid_check(*desc, *gd, B, ctx->geo.mono != 0, tw, th, &gs)) return rc;
+    uint64_t slot_bytes = 0;
+    if (const int rc = grid_check_layout(*desc, gs.e, gs.dw, gs.dh, &slot_bytes)) return rc;
+    if ((uint64_t)(uintptr_t)dev_dst % (uint64_t)gs.e.es) return P265R_EINVAL;
+    const uint64_t need = (uint64_t)(n_frames - 1) * desc->frame_bytes + slot_bytes;
+    if (b->runs == 0) return P265R_ESTATE;                  // (a recon-input batch whose filters never ran: no planes yet)
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto on_device = [&](const void* p) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+    };
+    if (!on_device(dev_dst)) return P265R_EINVAL;
+    if (need > dst_bytes) return P265R_ERANGE;
+    if (!on_device(static_cast<const unsigned char*>(dev_dst) + need - 1)) return P265R_EINVAL;
+    // ---- enqueue ---------------------------------------------------------------------------------
+    // quarter turns: pass 1 writes F into the batch's staging area (tight, 16-byte pitches), pass 2 transposes it
+    p265r_export_desc sd = *desc;
+    if (gs.transpose) {
+        grid_fill_layout(&sd, gs.e, gs.W, gs.H, 16);
+        const uint64_t stage = sd.frame_bytes * (uint64_t)n_frames;
+        if (stage > b->grid_stage_bytes) {
+            if (b->grid_stage) {                            // (an earlier call's transpose may still read it)
+                HIP_TRY(hipStreamSynchronize(b->stream));
+                HIP_TRY(hipFree(b->grid_stage));
+                b->grid_stage = nullptr;
+                b->grid_stage_bytes = 0;
+            }
+            HIP_TRY(hipMalloc(&b->grid_stage, (size_t)stage));
+            b->grid_stage_bytes = (size_t)stage;
+        }
+    }
+    GridArgs a{};
+    a.e.dst = gs.transpose ? static_cast<uint8_t*>(b->grid_stage) : static_cast<uint8_t*>(dev_dst);
+    a.e.frame_bytes = sd.frame_bytes;
+    for (int k = 0; k < 3; ++k) { a.e.plane_off[k] = sd.plane_off[k]; a.e.pitch[k] = sd.pitch[k]; }
+    a.e.crop_l = gs.wl; a.e.crop_t = gs.wt;
+    if (gs.e.rgb) {
+        p265r_export_desc dc = *desc;                       // (the coefficients do not depend on the crop)
+        dc.crop_left = dc.crop_right = dc.crop_top = dc.crop_bottom = 0;
+        if (const int rc = export_coefficients(dc, B, a.e.coef)) return rc;
+        a.e.fscale = (float)(1.0 / (double)((1 << B) - 1));
+    }
+    a.e.shift = desc->sample == P265R_SMP_MSB16 ? 16 - B : 0;
+    a.grey = (1 << (B - 1)) << a.e.shift;
+    a.rows = (int)gd->rows; a.cols = (int)gd->cols; a.tw = tw; a.th = th;
+    a.W = gs.W; a.H = gs.H; a.fx = gs.fx; a.fy = gs.fy;
+    {
+        // the tiles' plane addresses; the device copy lives until the lane is next synchronised, like a pic_index list
+        std::vector<uint64_t> tab((size_t)n * 3);
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k)
+                tab[(size_t)i * 3 + k] = (uint64_t)(uintptr_t)b->h_pics[(size_t)(pic_index ? pic_index[i] : i)].out[k];
+        void* d_tab = nullptr;
+        HIP_TRY(hipMalloc(&d_tab, sizeof(uint64_t) * tab.size()));
+        b->exp_idx.push_back(d_tab);
+        HIP_TRY(hipMemcpy(d_tab, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice));
+        a.tab = static_cast<const uint64_t*>(d_tab);
+    }
+    int rc = ctx->geo.pel16 ? launch_grid<uint16_t>(*desc, ctx->geo, a, n_frames, b->stream)
+                            : launch_grid<uint8_t>(*desc, ctx->geo, a, n_frames, b->stream);
+    if (rc) return rc;
+    ctx->lane_busy |= 1u << b->lane;
+    if (gs.transpose) {
+        GridTransposeArgs t{};
+        t.src = static_cast<const uint8_t*>(b->grid_stage);
+        t.dst = static_cast<uint8_t*>(dev_dst);
+        t.src_frame = sd.frame_bytes; t.dst_frame = desc->frame_bytes;
+        ExportPlane pl[3];
+        grid_planes(*desc, gs.e, gs.W, gs.H, pl);
+        for (int k = 0; k < gs.e.n_planes; ++k) {
+            t.src_off[k] = sd.plane_off[k]; t.dst_off[k] = desc->plane_off[k];
+            t.src_pitch[k] = sd.pitch[k]; t.dst_pitch[k] = desc->pitch[k];
+            const int c = desc->format == P265R_FMT_RGB_PACKED ? 3 : (desc->format == P265R_FMT_SEMIPLANAR && k == 1 ? 2 : 1);
+            t.w[k] = (int)(pl[k].row_bytes / (uint64_t)(gs.e.es * c));
+            t.h[k] = pl[k].rows;
+        }
+        t.tiles_y = (t.h[0] + kGridTile - 1) / kGridTile;
+        rc = launch_grid_transpose(*desc, gs.e.es, t, gs.e.n_planes, n_frames, b->stream);
+        if (rc) return rc;
+    }
+    return P265R_OK;
+}
+
 int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (!ctx || !b) return P265R_EINVAL;
     (void)hipSetDevice(ctx->device);
@@ -1522,6 +1688,7 @@ int p265r_batch_free(p265r_ctx* ctx, p265r_batch* b) {
     if (b->d_dig) (void)hipFree(b->d_dig);
     if (b->d_hash) (void)hipFree(b->d_hash);
     if (b->d_narrow) (void)hipFree(b->d_narrow);
+    if (b->grid_stage) (void)hipFree(b->grid_stage);
     for (void* p : b->exp_idx) (void)hipFree(p);
     if (b->mem) {
         // keep the larger of (cache, this allocation) for the next upload (its runs are complete)

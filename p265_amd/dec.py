@@ -16,6 +16,9 @@ area``) scales every frame of a GPU format to that size on the GPU (the scaled d
 ``i420`` host path does not scale and refuses both.  A stream whose luma and chroma bit depths differ takes the
 ``i420`` host path with ``--hash-on host`` only (the GPU formats and the GPU hash refuse it by name); when either
 depth exceeds 8 its file holds every plane as 16-bit little-endian samples, values unscaled.
+``--heif in.heic`` (instead of ``-b``) decodes a HEIF / HEIC still image: the grid is assembled, cut and oriented on the
+GPU (``--no-orientation`` ignores irot / imir), every ``--format`` is a GPU format there, ``--probe`` prints the
+container's description only.
 """
 import argparse
 import sys
@@ -29,7 +32,11 @@ FORMATS = ("i420", "nv12", "p010", "rgb24", "rgb-planar-f16")
 
 def parse_cmd(argv=None):
     ap = argparse.ArgumentParser(prog="p265_amd.dec")
-    ap.add_argument("-b", "--bitstream", required=True, help="The h.265 bitstream to be decoded.")
+    ap.add_argument("-b", "--bitstream", help="The h.265 bitstream to be decoded.")
+    ap.add_argument("--heif", metavar="FILE", help="A HEIF / HEIC still image to be decoded instead (p265_amd.heif): its "
+                    "primary item, grid assembled and orientation applied on the GPU; --format i420 is the GPU's planar form")
+    ap.add_argument("--no-orientation", action="store_true", help="--heif: ignore irot / imir")
+    ap.add_argument("--probe", action="store_true", help="--heif: print the container's description and decode nothing")
     ap.add_argument("-o", "--output", help="The reconstructed output (--format, default I420; cropped, output order).")
     ap.add_argument("--skip-syntax-dump", type=int, default=0, help="Accepted for compatibility; no effect.")
     ap.add_argument("--device", type=int, default=0)
@@ -45,7 +52,9 @@ def parse_cmd(argv=None):
     ap.add_argument("--format", choices=FORMATS, default="i420",
                     help="output format; anything but i420 is converted on the GPU (cropped, device-side output) and "
                          "copied back once per batch")
-    ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default="bt709", help="RGB formats: the YCbCr matrix")
+    ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default=None,
+                    help="RGB formats: the YCbCr matrix (default bt709; --heif: the file's colour description unless "
+                         "--matrix or --full-range is given)")
     ap.add_argument("--full-range", action="store_true", help="RGB formats: full-range YCbCr (default limited)")
     ap.add_argument("--upsample", choices=("nearest", "bilinear"), default="nearest", help="RGB formats: chroma upsampling")
     ap.add_argument("--mono-output", choices=("y", "i420"), default="y",
@@ -56,6 +65,13 @@ def parse_cmd(argv=None):
     ap.add_argument("--resize-filter", choices=("nearest", "bilinear", "area"), default=None,
                     help="the filter of --resize (default bilinear; area: exact box average, downscale only)")
     a = ap.parse_args(argv)
+    a.colour_given = a.matrix is not None or a.full_range      # (--heif: the command line's colour wins over the file's)
+    if a.matrix is None:
+        a.matrix = "bt709"
+    if (a.bitstream is None) == (a.heif is None):
+        ap.error("one of -b/--bitstream and --heif is required")
+    if a.heif is not None and a.resize is not None:
+        ap.error("--heif: scaled output of a HEIF image is not supported")
     if a.resize is not None or a.resize_filter is not None:
         if a.format == "i420":
             ap.error("--resize / --resize-filter scale on the GPU: choose a GPU --format (%s); the default i420 is the "
@@ -80,8 +96,28 @@ def export_spec(a):
     return recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample, **kw)
 
 
+def heif_main(a):
+    """--heif: probe, or decode the primary item and write the oriented frame's planes, rows tight."""
+    from . import heif
+    if a.probe:
+        print(heif.probe(a.heif))
+        return 0
+    named = recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample)
+    img = heif.decode(a.heif, export=named, device=a.device, apply_orientation=not a.no_orientation, aux=(),
+                      verify_hash=not a.no_verify, hash_on=a.hash_on, colour="spec" if a.colour_given else "file")
+    if a.output:
+        with open(a.output, "wb") as f:
+            f.write(img.frames.slot(0).tobytes())
+    print({"width": img.width, "height": img.height, "bit_depth": img.bit_depth, "orientation": img.orientation,
+           "colour": img.colour, "format": a.format, "icc": img.icc is not None})
+    img.frames.free()
+    return 0
+
+
 def main(argv=None):
     a = parse_cmd(argv)
+    if a.heif is not None:
+        return heif_main(a)
     t0 = time.time()
     st = decoder.decode_file(a.bitstream, a.output, device=a.device, batch=a.batch, threads=a.threads,
                              depth=a.depth, verify_hash=not a.no_verify, sparse_upload=a.sparse_upload,

@@ -187,9 +187,10 @@ class ExportLayout:
         """(shape, byte strides) of plane ``k`` of a picture of luma ``size`` = (width, height) before the crop; a
         scaled export: of its output size, whatever the picture's."""
         l, r, t, b = self.crop
-        w, h = int(size[0]) - l - r, int(size[1]) - t - b
         if self.size is not None:
             w, h = self.size
+        else:
+            w, h = int(size[0]) - l - r, int(size[1]) - t - b
         es, f = self.dtype.itemsize, self.desc.format
         if f == _lib.FMT_RGB_PACKED:
             return (h, w, 3), (self.pitch[0], 3 * es, es)
@@ -215,6 +216,46 @@ def export_layout(params, spec, size=None):
     _lib.check(_lib.load().p265r_export_layout(ctypes.byref(pc), w, h, ctypes.byref(d), int(spec.pitch_align)),
                "p265r_export_layout")
     return ExportLayout(d, int(params["bit_depth_luma"]), mono=R.is_mono(params))
+
+
+@dataclass(frozen=True)
+class GridSpec:
+    """A p265r_grid_desc: ``rows`` x ``cols`` pictures (row-major) form one canvas, of which ``out_width`` x
+    ``out_height`` is the image; the ExportSpec's crop is taken inside that image.  ``orientation`` = k | m << 2: the
+    frame is turned k quarter turns anticlockwise, then (m = 1) mirrored left-right -- np.rot90(F, k), then [:, ::-1]."""
+    rows: int
+    cols: int
+    out_width: int
+    out_height: int
+    orientation: int = 0
+
+    def desc(self):
+        g = _lib.GridDesc()
+        g.rows, g.cols, g.out_width, g.out_height = int(self.rows), int(self.cols), int(self.out_width), int(self.out_height)
+        g.orientation = int(self.orientation)
+        return g
+
+    def frame_size(self, crop=(0, 0, 0, 0)):
+        """(width, height) of the oriented frame under ``crop``."""
+        w, h = self.out_width - crop[0] - crop[1], self.out_height - crop[2] - crop[3]
+        return (h, w) if self.orientation & 1 else (w, h)
+
+
+def grid_layout(params, spec, grid, tile=None):
+    """ExportLayout of the frame a grid of ``tile`` = (width, height) pictures (default: the params' size) gives,
+    through the C p265r_grid_layout (host only: no context, no device).  Every plane view has the oriented frame's
+    size, whatever size is asked for."""
+    if spec.size is not None:
+        raise ValueError("a grid export is not scaled (ExportSpec.size)")
+    d, g = spec.desc(), grid.desc()
+    pc = _params_c(params)
+    tw, th = (0, 0) if tile is None else (int(tile[0]), int(tile[1]))
+    _lib.check(_lib.load().p265r_grid_layout(ctypes.byref(pc), tw, th, ctypes.byref(g), ctypes.byref(d), int(spec.pitch_align)),
+               "p265r_grid_layout")
+    lay = ExportLayout(d, int(params["bit_depth_luma"]), mono=R.is_mono(params))
+    lay.size = grid.frame_size(tuple(int(v) for v in spec.crop))
+    lay.grid = g
+    return lay
 
 
 def export_coefficients(spec, bit_depth):
@@ -654,6 +695,45 @@ class ReconContext:
                 buf.free()
             raise
         return DeviceFrames(dst, dst_bytes, lay, sizes, buffer=buf, ctx=self, batch=batch)
+
+    def grid_layout(self, spec, grid, tile=None):
+        """ExportLayout of the oriented frame of a grid of ``tile``-sized pictures (a records Picture, a (width,
+        height) pair, or None = the context's size)."""
+        if tile is not None and hasattr(tile, "ctus"):
+            pp = R.pic_params(self.params, tile)
+            tile = (int(pp["pic_width"]), int(pp["pic_height"]))
+        return grid_layout(self.params, spec, grid, tile)
+
+    def export_grid(self, batch, spec, grid, dst=None, dst_bytes=None, only=None):
+        """Enqueue, after the batch's runs, the assembly of ``grid.rows * grid.cols`` pictures per frame into frame
+        slots in device memory (p265r_batch_export_grid) and return at once -> DeviceFrames, one slot per frame.
+        ``only`` lists the pictures, tile r * cols + c of frame f at f * rows * cols + r * cols + c (None: the batch in
+        order); ``dst`` / ``dst_bytes`` as for ``export``."""
+        from . import hip
+        tiles = int(grid.rows) * int(grid.cols)
+        idx = list(range(len(batch.pics))) if only is None else [int(i) for i in only]
+        if tiles <= 0 or not idx or len(idx) % tiles or any(not 0 <= i < len(batch.pics) for i in idx):
+            raise _lib.P265RError(_lib.EINVAL, "p265r_batch_export_grid")
+        n_frames = len(idx) // tiles
+        lay = self.grid_layout(spec, grid, batch.pics[idx[0]])
+        buf = None
+        if dst is None:
+            hip.set_device(self.device)
+            dst_bytes = lay.frame_bytes * n_frames
+            buf = hip.DeviceBuffer(dst_bytes)
+            dst = buf.ptr.value
+        elif dst_bytes is None:
+            raise ValueError("dst_bytes: the size of the caller's buffer")
+        arr = (ctypes.c_int32 * len(idx))(*idx) if only is not None else None
+        try:
+            _lib.check(self.lib.p265r_batch_export_grid(self.handle, batch.handle, ctypes.byref(lay.desc), ctypes.byref(lay.grid),
+                                                        ctypes.c_void_p(int(dst)), int(dst_bytes), arr, n_frames),
+                       "p265r_batch_export_grid")
+        except BaseException:
+            if buf is not None:
+                buf.free()
+            raise
+        return DeviceFrames(dst, dst_bytes, lay, [lay.size] * n_frames, buffer=buf, ctx=self, batch=batch)
 
     def sync(self):
         _lib.check(self.lib.p265r_sync(self.handle), "p265r_sync")
