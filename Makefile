@@ -8,9 +8,11 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -shared -Wall -Wno-unused-function -mllvm -structurizecfg-skip-uniform-regions=true
 # (sparse_host.cpp, upload_host.cpp: the host-only parts of the upload, plain C++ -- see sparse-check, upload-check;
 # export_host.cpp, resize_host.cpp: the host-only parts of the device-side output and its scaled form;
-# pichash_host.cpp: the picture hash of a host plane; grid_host.cpp: the host-only part of the grid export)
+# pichash_host.cpp: the picture hash of a host plane; grid_host.cpp, grid_resize_host.cpp: the host-only parts of the
+# grid export and its scaled, ragged form)
 SRC := p265_amd/csrc/p265r.hip p265_amd/csrc/sparse_host.cpp p265_amd/csrc/upload_host.cpp p265_amd/csrc/export_host.cpp \
-       p265_amd/csrc/pichash_host.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/grid_host.cpp
+       p265_amd/csrc/pichash_host.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/grid_host.cpp \
+       p265_amd/csrc/grid_resize_host.cpp
 HDR := $(wildcard p265_amd/csrc/*.h) include/p265r.h
 
 CXX ?= g++
@@ -49,7 +51,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check tools/resize_check tools/prep_check tools/grid_check
+	rm -f p265_amd/libp265r.so p265_amd/libp265fe.so p265_amd/libp265probe.so $(CHECKVARIANTS) tools/sparse_check tools/upload_check tools/export_check tools/hash_check tools/mono_check tools/resize_check tools/prep_check tools/grid_check tools/grid_resize_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
@@ -115,6 +117,20 @@ grid-check: tools/grid_check.cpp p265_amd/csrc/grid_host.cpp p265_amd/csrc/expor
 		-o tools/grid_check tools/grid_check.cpp p265_amd/csrc/grid_host.cpp p265_amd/csrc/export_host.cpp
 	./tools/grid_check
 .PHONY: grid-check
+
+# host sanitizer check of the scaled grid export's host code (every refusal, the per-frame constants against a
+# restatement of the orientation rule, the tile-width reciprocal at every step): a stand-alone CPU program, not part
+# of `all`
+GRID_RESIZE_CHECK ?= tools/grid_resize_check
+grid-resize-check: tools/grid_resize_check.cpp p265_amd/csrc/grid_resize_host.cpp p265_amd/csrc/grid_host.cpp \
+                   p265_amd/csrc/resize_host.cpp p265_amd/csrc/export_host.cpp p265_amd/csrc/grid_resize_host.h \
+                   p265_amd/csrc/grid_host.h p265_amd/csrc/resize_host.h p265_amd/csrc/resize_math.h \
+                   p265_amd/csrc/export_host.h include/p265r.h
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+		-o $(GRID_RESIZE_CHECK) tools/grid_resize_check.cpp p265_amd/csrc/grid_resize_host.cpp \
+		p265_amd/csrc/grid_host.cpp p265_amd/csrc/resize_host.cpp p265_amd/csrc/export_host.cpp
+	$(GRID_RESIZE_CHECK)
+.PHONY: grid-resize-check
 
 # host check of job prep's short cuts (intra_prep.h prep_avail_clear, prep_filter_min_lg) against the generic
 # arithmetic, exhaustive: a stand-alone CPU program (hipcc, run without a GPU), not part of `all`

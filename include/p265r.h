@@ -465,6 +465,57 @@ int  p265r_batch_export_grid(p265r_ctx* ctx, p265r_batch* batch, const p265r_exp
                              const p265r_grid_desc* grid, void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index,
                              int n_frames);
 
+/* ---- scaled grid export: every frame a grid of its own, every slot out_width x out_height ----------------------
+ * No counterpart in the reference.  What a folder of HEIF photos asks for: grids of differing shape, window and
+ * orientation into one dense batch.  For one frame, with rows x cols tiles of own size tw x th:
+ *   Canvas and window.  As p265r_batch_export_grid defines them: the canvas is cols tw x rows th, the window
+ *     [crop_left, out_width - crop_right) x [crop_top, out_height - crop_bottom) of it, W x H; here the crop is the
+ *     FRAME's (p265r_grid_frame), and desc->crop_* must be 0.
+ *   Pre-turn size.  With ow x oh = the resize descriptor's output size and orientation = k | m << 2:
+ *     (pw, ph) = (ow, oh) for k even, (oh, ow) for k odd.
+ *   R.  Exactly what p265r_batch_export_resized would write if the canvas were one decoded picture, the window its
+ *     crop and the output size pw x ph: the step / U(h) positions, NEAREST, BILINEAR and AREA, the chroma siting, the
+ *     MSB16 shift, the CbCr interleave, the integer RGB conversion and fl32(fl32(v scale) + bias) under P265R_RS_NORM
+ *     carry over unchanged.  Taps are clamped to THE WINDOW: they cross tile seams inside it and never read outside it.
+ *   Destination slot.  np.rot90(R, k), then [:, ::-1] when m is set.  Every plane is turned alike; a CbCr pair or an
+ *     RGB triple moves as one element; chroma is NOT re-sited after a turn (the words of the grid export).
+ *   Slot size.  Every slot is ow x oh, whatever its frame's grid, window or orientation; its layout is
+ *     p265r_resize_layout's.
+ *   Two identities, byte for byte: rows = cols = 1 with orientation 0 equals p265r_batch_export_resized with that
+ *     crop; NEAREST with pw x ph = W x H equals p265r_batch_export_grid with P265R_UP_NEAREST.
+ *   A chroma plane's window is W/2 x H/2 at (crop_left/2, crop_top/2): on a 4:2:0 source the window is even on both
+ *     axes for EVERY format (an odd one would give the filters half a chroma sample, and break the second identity
+ *     in the last column).  A monochrome source has no such limit except for semi-planar output. */
+typedef struct p265r_grid_frame {      /* one frame of a ragged grid export */
+    uint32_t rows, cols;               /* 1..256 */
+    uint32_t out_width, out_height;    /* the grid item's size on ITS canvas */
+    uint32_t crop_left, crop_right, crop_top, crop_bottom;   /* the window, per frame */
+    uint32_t orientation;              /* k | m << 2 */
+    uint32_t reserved[3];              /* 0 */
+} p265r_grid_frame;
+
+/* host only, no context: validates desc, rs and frames[0..n_frames) against a tile size (0: the params' size) as
+ * p265r_batch_export_grid_resized does before it looks at a batch, and writes the constants its kernels use, twelve
+ * int32 per frame: {first tile, cols, window left, top, W, H, pw, ph, reverse x, reverse y, transpose, index in the
+ * staging area or -1}.  R is written reversed along x / y and then, for k odd, transposed:
+ *   k = 0: (m, 0)   k = 2: (!m, 1)   k = 1: (1, m), transposed   k = 3: (0, !m), transposed */
+int  p265r_grid_resize_plan(const p265r_params* params, int tile_width, int tile_height, const p265r_export_desc* desc,
+                            const p265r_resize_desc* rs, const p265r_grid_frame* frames, int n_frames, int32_t* out);
+/* as p265r_batch_export_grid and p265r_batch_export_resized: enqueued on the batch's lane behind its runs, no stream
+ * of its own, returns without waiting, every check on the host before a launch.  At most TWO kernel launches whatever
+ * the mix of orientations: frames with k even are written straight to their slot; frames with k odd go through the
+ * grid export's staging area (allocated once per batch, reused, grown only when needed) and one transpose launch.
+ * pic_index lists the tiles frame after frame: frame f's tiles start at the sum of rows * cols of the frames before
+ * it; NULL = the batch in order (the sum over all frames must then equal the batch's pictures).
+ * P265R_EINVAL: everything p265r_batch_export_resized and p265r_batch_export_grid refuse, applied per frame (listed
+ * pictures of differing own sizes across the whole call included); desc->crop_* non-zero; a window above 32767 on an
+ * axis; P265R_RS_AREA with pw > W or ph > H, or with a window above 8192 on an axis; an odd window on a 4:2:0
+ * source; n_frames or the tiles listed above 65535.  P265R_EUNSUPPORTED for a context of unequal depths.  Monochrome
+ * contexts follow the monochrome rules of the two existing exports. */
+int  p265r_batch_export_grid_resized(p265r_ctx* ctx, p265r_batch* batch, const p265r_export_desc* desc,
+                                     const p265r_resize_desc* rs, const p265r_grid_frame* frames, int n_frames,
+                                     void* dev_dst, uint64_t dst_bytes, const int32_t* pic_index);
+
 /* ---- device-side picture hash: the decoded_picture_hash SEI values (D.3.19) computed in device memory ----
  * No counterpart in the reference (no SEI support, nalu.py:130-131).  The hash of a plane runs over its
  * pictureData: the samples of the picture's OWN size (uncropped) in raster order, one byte per sample at

@@ -90,6 +90,14 @@ class GridDesc(ctypes.Structure):
                 ("out_height", ctypes.c_uint32), ("orientation", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
+class GridFrame(ctypes.Structure):
+    """p265r_grid_frame (one frame of the scaled, ragged grid export)."""
+    _fields_ = [("rows", ctypes.c_uint32), ("cols", ctypes.c_uint32), ("out_width", ctypes.c_uint32),
+                ("out_height", ctypes.c_uint32), ("crop_left", ctypes.c_uint32), ("crop_right", ctypes.c_uint32),
+                ("crop_top", ctypes.c_uint32), ("crop_bottom", ctypes.c_uint32), ("orientation", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
 # p265r_resize_desc filters and flags
 RS_NEAREST, RS_BILINEAR, RS_AREA = 0, 1, 2
 RS_NORM = 1
@@ -103,7 +111,7 @@ HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
 HASH_BYTES = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 
 assert ctypes.sizeof(Params) == 32 and ctypes.sizeof(PictureC) == 104 and ctypes.sizeof(ExportDesc) == 88
-assert ctypes.sizeof(ResizeDesc) == 40 and ctypes.sizeof(GridDesc) == 32
+assert ctypes.sizeof(ResizeDesc) == 40 and ctypes.sizeof(GridDesc) == 32 and ctypes.sizeof(GridFrame) == 48
 
 # every symbol include/p265r.h declares, with (restype, argtypes)
 _vp = ctypes.c_void_p
@@ -142,6 +150,12 @@ SIGNATURES = {
                                          ctypes.POINTER(ExportDesc), ctypes.c_uint32]),
     "p265r_batch_export_grid": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), ctypes.POINTER(GridDesc), _vp,
                                                ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    "p265r_grid_resize_plan": (ctypes.c_int, [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ExportDesc),
+                                              ctypes.POINTER(ResizeDesc), ctypes.POINTER(GridFrame), ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int32)]),
+    "p265r_batch_export_grid_resized": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ExportDesc), ctypes.POINTER(ResizeDesc),
+                                                       ctypes.POINTER(GridFrame), ctypes.c_int, _vp, ctypes.c_uint64,
+                                                       ctypes.POINTER(ctypes.c_int32)]),
     "p265r_batch_hash_async": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "p265r_batch_hash_read": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]),
     "p265r_plane_hash_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,

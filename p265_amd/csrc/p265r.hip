@@ -27,6 +27,8 @@
 #include "resize_host.h"
 #include "grid.h"
 #include "grid_host.h"
+#include "grid_resize.h"
+#include "grid_resize_host.h"
 #include "intra.h"
 #include "intra_prep.h"
 #include "intra_rows.h"
@@ -570,6 +572,65 @@ int launch_grid_transpose(const p265r_export_desc& d, int es, const GridTranspos
         if (d.format == P265R_FMT_RGB_PACKED) grid_transpose_kernel<U, 3, 3><<<grid, 256, 0, st>>>(a);
         else if (d.format == P265R_FMT_SEMIPLANAR) grid_transpose_kernel<U, 1, 2><<<grid, 256, 0, st>>>(a);
         else grid_transpose_kernel<U, 1, 1><<<grid, 256, 0, st>>>(a);
+    };
+    if (es == 1) go(std::enable_if<true, uint8_t>{});
+    else if (es == 2) go(std::enable_if<true, uint16_t>{});
+    else go(std::enable_if<true, uint32_t>{});
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// Pass 1 of p265r_batch_export_grid_resized on stream st: n frames, the largest R mw x mh.
+template <typename S>
+int launch_grid_resize(const p265r_export_desc& d, uint32_t filter, const Geo& g, const GridRsArgs& a, int mw, int mh, int n,
+                       hipStream_t st) {
+    const auto blocks = [](int rows) { return (rows + kExportRows - 1) / kExportRows; };
+    const auto grid = [&](int group, int row_blocks) {
+        return dim3((unsigned)((mw / group + 2 + kExportLanes - 1) / kExportLanes), (unsigned)row_blocks, (unsigned)n);
+    };
+    const auto by_filter = [&](auto&& go) {
+        if (filter == P265R_RS_NEAREST) go(std::integral_constant<int, (int)kRsNearest>{});
+        else if (filter == P265R_RS_BILINEAR) go(std::integral_constant<int, (int)kRsBilinear>{});
+        else go(std::integral_constant<int, (int)kRsArea>{});
+    };
+    if (d.format == P265R_FMT_PLANAR || d.format == P265R_FMT_SEMIPLANAR) {
+        const int semi = d.format == P265R_FMT_SEMIPLANAR ? 1 : 0;
+        const int chroma_blocks = semi ? blocks(mh / 2) : (g.mono ? 0 : 2 * blocks(mh / 2));
+        by_filter([&](auto f) {
+            grid_resize_yuv_kernel<S, decltype(f)::value><<<grid(16 / (int)sizeof(S), blocks(mh) + chroma_blocks), 256, 0, st>>>(
+                g, a, semi);
+        });
+    } else {
+        auto rgb = [&](auto dtag) {
+            using D = typename decltype(dtag)::type;
+            by_filter([&](auto f) {
+                constexpr int F = decltype(f)::value;
+                if (d.format == P265R_FMT_RGB_PACKED)
+                    grid_resize_rgb_kernel<S, D, true, F><<<grid(sizeof(D) == 1 ? 16 : 8, blocks(mh)), 256, 0, st>>>(g, a);
+                else
+                    grid_resize_rgb_kernel<S, D, false, F><<<grid(sizeof(D) == 1 ? 16 : 8, blocks(mh)), 256, 0, st>>>(g, a);
+            });
+        };
+        switch (d.sample) {
+            case P265R_SMP_U8: rgb(std::enable_if<true, uint8_t>{}); break;
+            case P265R_SMP_F16: rgb(std::enable_if<true, _Float16>{}); break;
+            case P265R_SMP_F32: rgb(std::enable_if<true, float>{}); break;
+            default: rgb(std::enable_if<true, S>{}); break;                       // NATIVE
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return P265R_OK;
+}
+
+// Pass 2: the staged frames of a ragged call transposed into their slots (the others' blocks return at once).
+int launch_grid_resize_transpose(const p265r_export_desc& d, int es, const GridTransposeArgs& a, const GridRsFrame* frames,
+                                 int n_planes, int n, hipStream_t st) {
+    const dim3 grid((unsigned)((a.w[0] + kGridTile - 1) / kGridTile), (unsigned)(n_planes * a.tiles_y), (unsigned)n);
+    auto go = [&](auto utag) {
+        using U = typename decltype(utag)::type;
+        if (d.format == P265R_FMT_RGB_PACKED) grid_resize_transpose_kernel<U, 3, 3><<<grid, 256, 0, st>>>(a, frames);
+        else if (d.format == P265R_FMT_SEMIPLANAR) grid_resize_transpose_kernel<U, 1, 2><<<grid, 256, 0, st>>>(a, frames);
+        else grid_resize_transpose_kernel<U, 1, 1><<<grid, 256, 0, st>>>(a, frames);
     };
     if (es == 1) go(std::enable_if<true, uint8_t>{});
     else if (es == 2) go(std::enable_if<true, uint16_t>{});
@@ -1672,6 +1733,135 @@ int p265r_batch_export_grid(p265r_ctx* ctx, p265r_batch* b, const p265r_export_d
         }
         t.tiles_y = (t.h[0] + kGridTile - 1) / kGridTile;
         rc = launch_grid_transpose(*desc, gs.e.es, t, gs.e.n_planes, n_frames, b->stream);
+        if (rc) return rc;
+    }
+    return P265R_OK;
+}
+
+int p265r_batch_export_grid_resized(p265r_ctx* ctx, p265r_batch* b, const p265r_export_desc* desc, const p265r_resize_desc* rs,
+                                    const p265r_grid_frame* frames, int n_frames, void* dev_dst, uint64_t dst_bytes,
+                                    const int32_t* pic_index) {
+    if (!ctx || !b || !desc || !rs || !frames || !dev_dst) return P265R_EINVAL;
+    // ---- host checks: nothing is launched unless all of them pass ----------------------------
+    if (n_frames <= 0 || n_frames > 65535) return P265R_EINVAL;
+    const int B = ctx->params.bit_depth_luma;
+    if (ctx->geo.bd[0] != ctx->geo.bd[1]) return P265R_EUNSUPPORTED;   // unequal bit depths
+    int64_t n64 = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        if (frames[f].rows < 1 || frames[f].rows > 256 || frames[f].cols < 1 || frames[f].cols > 256) return P265R_EINVAL;
+        n64 += (int64_t)(frames[f].rows * frames[f].cols);
+    }
+    // (NULL = the batch in order: the frames must then account for every picture of it)
+    if (n64 > 65535 || n64 > b->n_pics || (!pic_index && n64 != b->n_pics)) return P265R_EINVAL;
+    const int n = (int)n64;
+    std::vector<char> seen(pic_index ? (size_t)b->n_pics : 0, 0);
+    int tw = 0, th = 0;
+    for (int i = 0; i < n; ++i) {
+        const int pic = pic_index ? pic_index[i] : i;
+        if (pic < 0 || pic >= b->n_pics) return P265R_EINVAL;
+        if (pic_index) {
+            if (seen[(size_t)pic]) return P265R_EINVAL;
+            seen[(size_t)pic] = 1;
+        }
+        if (i == 0) { tw = b->size[(size_t)pic][0]; th = b->size[(size_t)pic][1]; }
+        else if (b->size[(size_t)pic][0] != tw || b->size[(size_t)pic][1] != th) return P265R_EINVAL;
+    }
+    GridRsPlan plan;
+    if (const int rc = grid_resize_plan(*desc, *rs, frames, n_frames, B, ctx->geo.mono != 0, tw, th, &plan)) return rc;
+    uint64_t slot_bytes = 0;
+    if (const int rc = resize_check_layout(*desc, plan.e, *rs, &slot_bytes)) return rc;
+    if ((uint64_t)(uintptr_t)dev_dst % (uint64_t)plan.e.es) return P265R_EINVAL;
+    const uint64_t need = (uint64_t)(n_frames - 1) * desc->frame_bytes + slot_bytes;
+    if (b->runs == 0) return P265R_ESTATE;                  // (a recon-input batch whose filters never ran: no planes yet)
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto on_device = [&](const void* p) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+    };
+    if (!on_device(dev_dst)) return P265R_EINVAL;
+    if (need > dst_bytes) return P265R_ERANGE;
+    if (!on_device(static_cast<const unsigned char*>(dev_dst) + need - 1)) return P265R_EINVAL;
+    // ---- enqueue ---------------------------------------------------------------------------------
+    // quarter turns: pass 1 writes those frames' R (ow rows of oh) into the batch's staging area (tight, 16-byte
+    // pitches), pass 2 transposes them
+    p265r_export_desc sd = *desc;
+    if (plan.n_stage) {
+        grid_fill_layout(&sd, plan.e, plan.oh, plan.ow, 16);
+        const uint64_t stage = sd.frame_bytes * (uint64_t)plan.n_stage;
+        if (stage > b->grid_stage_bytes) {
+            if (b->grid_stage) {                            // (an earlier call's transpose may still read it)
+                HIP_TRY(hipStreamSynchronize(b->stream));
+                HIP_TRY(hipFree(b->grid_stage));
+                b->grid_stage = nullptr;
+                b->grid_stage_bytes = 0;
+            }
+            HIP_TRY(hipMalloc(&b->grid_stage, (size_t)stage));
+            b->grid_stage_bytes = (size_t)stage;
+        }
+    }
+    GridRsArgs a{};
+    a.r.e.dst = static_cast<uint8_t*>(dev_dst);
+    a.r.e.frame_bytes = desc->frame_bytes;
+    for (int k = 0; k < 3; ++k) {
+        a.r.e.plane_off[k] = desc->plane_off[k]; a.r.e.pitch[k] = desc->pitch[k];
+        a.st_off[k] = sd.plane_off[k]; a.st_pitch[k] = sd.pitch[k];
+    }
+    if (plan.e.rgb) {
+        p265r_export_desc dc = *desc;                       // (the coefficients do not depend on upsample)
+        dc.upsample = P265R_UP_NEAREST;
+        if (const int rc = export_coefficients(dc, B, a.r.e.coef)) return rc;
+    }
+    a.r.e.shift = desc->sample == P265R_SMP_MSB16 ? 16 - B : 0;
+    a.r.ow = plan.ow; a.r.oh = plan.oh;
+    a.r.grey = (1 << (B - 1)) << a.r.e.shift;
+    resize_norm(*rs, B, a.r.scale, a.r.bias);
+    a.tw = tw; a.th = th;
+    a.rcp_w[0] = grid_rs_rcp((uint32_t)tw); a.rcp_w[1] = grid_rs_rcp((uint32_t)tw >> 1);
+    a.rcp_h[0] = grid_rs_rcp((uint32_t)th); a.rcp_h[1] = grid_rs_rcp((uint32_t)th >> 1);
+    {
+        // one device block: the tiles' plane addresses, then the frames' entries; it lives until the lane is next
+        // synchronised, like a pic_index list
+        const size_t tab_words = (size_t)n * 3;
+        std::vector<uint64_t> blk(tab_words + (size_t)n_frames * (sizeof(GridRsFrame) / sizeof(uint64_t)));
+        static_assert(sizeof(GridRsFrame) == 48, "six 64-bit words per table entry");
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k)
+                blk[(size_t)i * 3 + k] = (uint64_t)(uintptr_t)b->h_pics[(size_t)(pic_index ? pic_index[i] : i)].out[k];
+        for (int f = 0; f < n_frames; ++f) {
+            GridRsFrame& o = plan.frames[(size_t)f];
+            o.dst = plan.stage[(size_t)f] >= 0
+                        ? (uint64_t)(uintptr_t)b->grid_stage + (uint64_t)plan.stage[(size_t)f] * sd.frame_bytes
+                        : (uint64_t)(uintptr_t)dev_dst + (uint64_t)f * desc->frame_bytes;
+        }
+        std::memcpy(blk.data() + tab_words, plan.frames.data(), sizeof(GridRsFrame) * (size_t)n_frames);
+        void* d_blk = nullptr;
+        HIP_TRY(hipMalloc(&d_blk, sizeof(uint64_t) * blk.size()));
+        b->exp_idx.push_back(d_blk);
+        HIP_TRY(hipMemcpy(d_blk, blk.data(), sizeof(uint64_t) * blk.size(), hipMemcpyHostToDevice));
+        a.tab = static_cast<const uint64_t*>(d_blk);
+        a.frames = reinterpret_cast<const GridRsFrame*>(a.tab + tab_words);
+    }
+    int rc = ctx->geo.pel16
+                 ? launch_grid_resize<uint16_t>(*desc, rs->filter, ctx->geo, a, plan.max_pw, plan.max_ph, n_frames, b->stream)
+                 : launch_grid_resize<uint8_t>(*desc, rs->filter, ctx->geo, a, plan.max_pw, plan.max_ph, n_frames, b->stream);
+    if (rc) return rc;
+    ctx->lane_busy |= 1u << b->lane;
+    if (plan.n_stage) {
+        GridTransposeArgs t{};
+        t.dst = static_cast<uint8_t*>(dev_dst);
+        t.dst_frame = desc->frame_bytes;
+        ExportPlane pl[3];
+        grid_planes(*desc, plan.e, plan.oh, plan.ow, pl);   // the staged planes: R of a quarter turn
+        for (int k = 0; k < plan.e.n_planes; ++k) {
+            t.src_off[k] = sd.plane_off[k]; t.dst_off[k] = desc->plane_off[k];
+            t.src_pitch[k] = sd.pitch[k]; t.dst_pitch[k] = desc->pitch[k];
+            const int c = desc->format == P265R_FMT_RGB_PACKED ? 3 : (desc->format == P265R_FMT_SEMIPLANAR && k == 1 ? 2 : 1);
+            t.w[k] = (int)(pl[k].row_bytes / (uint64_t)(plan.e.es * c));
+            t.h[k] = pl[k].rows;
+        }
+        t.tiles_y = (t.h[0] + kGridTile - 1) / kGridTile;
+        rc = launch_grid_resize_transpose(*desc, plan.e.es, t, a.frames, plan.e.n_planes, n_frames, b->stream);
         if (rc) return rc;
     }
     return P265R_OK;

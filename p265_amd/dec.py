@@ -18,7 +18,9 @@ area``) scales every frame of a GPU format to that size on the GPU (the scaled d
 depth exceeds 8 its file holds every plane as 16-bit little-endian samples, values unscaled.
 ``--heif in.heic`` (instead of ``-b``) decodes a HEIF / HEIC still image: the grid is assembled, cut and oriented on the
 GPU (``--no-orientation`` ignores irot / imir), every ``--format`` is a GPU format there, ``--probe`` prints the
-container's description only.
+container's description only.  ``--resize WxH --resize-filter ...`` scales it on the GPU too (the scaled grid export) and
+then takes several files, of any grid shape, window and orientation over one set of sequence parameters: their
+frames, all W x H, are written one after another.
 """
 import argparse
 import sys
@@ -33,8 +35,11 @@ FORMATS = ("i420", "nv12", "p010", "rgb24", "rgb-planar-f16")
 def parse_cmd(argv=None):
     ap = argparse.ArgumentParser(prog="p265_amd.dec")
     ap.add_argument("-b", "--bitstream", help="The h.265 bitstream to be decoded.")
-    ap.add_argument("--heif", metavar="FILE", help="A HEIF / HEIC still image to be decoded instead (p265_amd.heif): its "
-                    "primary item, grid assembled and orientation applied on the GPU; --format i420 is the GPU's planar form")
+    ap.add_argument("--heif", metavar="FILE", nargs="+",
+                    help="A HEIF / HEIC still image to be decoded instead (p265_amd.heif): its primary item, grid assembled "
+                    "and orientation applied on the GPU; --format i420 is the GPU's planar form.  With --resize several "
+                    "files (one set of sequence parameters and tile size) are decoded into frames of that one size, "
+                    "written one after another")
     ap.add_argument("--no-orientation", action="store_true", help="--heif: ignore irot / imir")
     ap.add_argument("--probe", action="store_true", help="--heif: print the container's description and decode nothing")
     ap.add_argument("-o", "--output", help="The reconstructed output (--format, default I420; cropped, output order).")
@@ -70,10 +75,10 @@ def parse_cmd(argv=None):
         a.matrix = "bt709"
     if (a.bitstream is None) == (a.heif is None):
         ap.error("one of -b/--bitstream and --heif is required")
-    if a.heif is not None and a.resize is not None:
-        ap.error("--heif: scaled output of a HEIF image is not supported")
+    if a.heif is not None and len(a.heif) > 1 and (a.resize is None or a.probe):
+        ap.error("--heif: several files need --resize WxH (frames of one size)")
     if a.resize is not None or a.resize_filter is not None:
-        if a.format == "i420":
+        if a.format == "i420" and a.heif is None:
             ap.error("--resize / --resize-filter scale on the GPU: choose a GPU --format (%s); the default i420 is the "
                      "host path and does not scale" % ", ".join(FORMATS[1:]))
         if a.resize is None:
@@ -97,20 +102,23 @@ def export_spec(a):
 
 
 def heif_main(a):
-    """--heif: probe, or decode the primary item and write the oriented frame's planes, rows tight."""
+    """--heif: probe, or decode the primary item(s) and write the oriented (--resize: scaled) frames' planes, rows tight."""
     from . import heif
     if a.probe:
-        print(heif.probe(a.heif))
+        print(heif.probe(a.heif[0]))
         return 0
-    named = recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample)
-    img = heif.decode(a.heif, export=named, device=a.device, apply_orientation=not a.no_orientation, aux=(),
-                      verify_hash=not a.no_verify, hash_on=a.hash_on, colour="spec" if a.colour_given else "file")
+    kw = dict(size=a.resize, resize=a.resize_filter or "bilinear") if a.resize is not None else {}
+    named = recon.ExportSpec.named(a.format, matrix=a.matrix, full_range=a.full_range, upsample=a.upsample, **kw)
+    imgs = heif.decode_many(a.heif, export=named, device=a.device, apply_orientation=not a.no_orientation, aux=(),
+                            verify_hash=not a.no_verify, hash_on=a.hash_on, colour="spec" if a.colour_given else "file")
     if a.output:
         with open(a.output, "wb") as f:
-            f.write(img.frames.slot(0).tobytes())
-    print({"width": img.width, "height": img.height, "bit_depth": img.bit_depth, "orientation": img.orientation,
-           "colour": img.colour, "format": a.format, "icc": img.icc is not None})
-    img.frames.free()
+            for img in imgs:
+                f.write(img.frames.slot(img.index).tobytes())
+    for img in imgs:
+        print({"width": img.width, "height": img.height, "bit_depth": img.bit_depth, "orientation": img.orientation,
+               "colour": img.colour, "format": a.format, "icc": img.icc is not None})
+    imgs[0].frames.free()
     return 0
 
 

@@ -566,6 +566,7 @@ class HeifImage:
     icc: object
     timing: dict = dataclasses.field(default_factory=dict)
     index: int = 0              # decode_many: this image's slot in ``frames``
+    source_size: object = None  # (width, height) of the oriented image before any resize; width / height are the slot's
 
 
 def _parse(src, item, aux, apply_orientation):
@@ -593,7 +594,8 @@ def _parse(src, item, aux, apply_orientation):
 
 
 def _decode_items(jobs, export, device, verify_hash, hash_on, colour, timing):
-    """jobs: [(container, ImageInfo)] of equally shaped images -> (DeviceFrames of len(jobs) slots, colour)."""
+    """jobs: [(container, ImageInfo)] of equally shaped images -- with ``export.size`` of any shape, over one set of
+    sequence parameters -> (DeviceFrames of len(jobs) slots, colour)."""
     import time
     from . import bitstream, recon
     from . import records as R
@@ -612,12 +614,13 @@ def _decode_items(jobs, export, device, verify_hash, hash_on, colour, timing):
                 raise UnsupportedHeif("images / tiles with differing sequence parameters cannot share a batch")
             if d.crop[0] or d.crop[2]:
                 raise UnsupportedHeif("a conformance window with a left / top offset is not supported in a HEIF item")
-        if (info.rows, info.cols, info.window, info.orientation, info.width, info.height) != \
+        if export.size is None and (info.rows, info.cols, info.window, info.orientation, info.width, info.height) != \
                 (info0.rows, info0.cols, info0.window, info0.orientation, info0.width, info0.height):
             raise UnsupportedHeif("decode_many: the images are not equally shaped")
     tw, th = int(first.params["pic_width"]), int(first.params["pic_height"])
-    if (tw - first.crop[1], th - first.crop[3]) != tuple(info0.tile_size) and len(info0.tiles) > 1:
-        raise UnsupportedHeif("grid tiles whose conformance window differs from their coded size are not supported")
+    for _, info in (jobs if export.size is not None else jobs[:1]):
+        if (tw - first.crop[1], th - first.crop[3]) != tuple(info.tile_size) and len(info.tiles) > 1:
+            raise UnsupportedHeif("grid tiles whose conformance window differs from their coded size are not supported")
     if colour == "spec":
         col = (export.matrix, bool(export.full_range))
     elif info0.colour is not None:
@@ -626,9 +629,17 @@ def _decode_items(jobs, export, device, verify_hash, hash_on, colour, timing):
         col = colour_of(first.colour[0], first.colour[1], "SPS VUI")
     else:
         col = DEFAULT_COLOUR
-    x, y, w, h = info0.window
-    spec = dataclasses.replace(export, matrix=col[0], full_range=col[1], crop=(x, info0.width - x - w, y, info0.height - y - h))
-    grid = recon.GridSpec(info0.rows, info0.cols, info0.width, info0.height, info0.orientation)
+    def crop_of(info):
+        x, y, w, h = info.window
+        return (x, info.width - x - w, y, info.height - y - h)
+    if export.size is None:
+        spec = dataclasses.replace(export, matrix=col[0], full_range=col[1], crop=crop_of(info0))
+        grid = recon.GridSpec(info0.rows, info0.cols, info0.width, info0.height, info0.orientation)
+    else:
+        # one slot of export.size per image, whatever its grid, window or orientation (a single item: a 1 x 1 grid)
+        spec = dataclasses.replace(export, matrix=col[0], full_range=col[1], crop=(0, 0, 0, 0))
+        grid = [recon.GridFrame(info.rows, info.cols, info.width, info.height, crop_of(info), info.orientation)
+                for _, info in jobs]
     flat = [d for dec in pics for d in dec]
     ctx = recon.ReconContext(first.params, device=device, scaling=first.scaling)
     try:
@@ -638,7 +649,7 @@ def _decode_items(jobs, export, device, verify_hash, hash_on, colour, timing):
             _verify(ctx, batch, flat, hash_on, bitstream, R)
         ctx.status(batch)
         t2 = time.perf_counter()
-        frames = ctx.export_grid(batch, spec, grid)
+        frames = ctx.export_grid(batch, spec, grid) if export.size is None else ctx.export_grid_resized(batch, spec, grid)
         ctx.status(batch)
         frames.detach()
         t3 = time.perf_counter()
@@ -676,25 +687,37 @@ def decode(src, export=None, device=0, item=None, aux=("alpha",), apply_orientat
 def decode_many(srcs, export=None, device=0, item=None, aux=(), apply_orientation=True, verify_hash=True,
                 hash_on="host", colour="file"):
     """Equally shaped images: one upload, one run, ONE grid-export call; -> [HeifImage] sharing one DeviceFrames of
-    len(srcs) slots (``frames.batch_array()`` is the dense view), image i in slot ``index`` = i."""
+    len(srcs) slots (``frames.batch_array()`` is the dense view), image i in slot ``index`` = i.  With ``export.size``
+    (and ``resize``, ``scale``, ``bias``) the images may differ in grid shape, item size, clap window and orientation --
+    grids and single items alike: every slot has that size (the scaled grid export); they must still share their
+    sequence parameters and tile size, because they share one context."""
     import time
     from . import recon
     if export is None:
         export = recon.ExportSpec.named("rgb24")
-    if export.size is not None:
-        raise UnsupportedHeif("scaled output (ExportSpec.size) of a HEIF image is not supported")
     timing = {}
     t0 = time.perf_counter()
     parsed = [_parse(s, item, aux, apply_orientation) for s in srcs]
     if not parsed:
         return []
     timing["container"] = time.perf_counter() - t0
+    with_alpha = all(a is not None for _, _, a in parsed)
+    alpha_spec = recon.ExportSpec(format="planar")
+    if export.size is not None and with_alpha:
+        # the alpha image goes through the same call: planar, plane 0, the slot's size
+        alpha_spec = recon.ExportSpec(format="planar", size=export.size, resize=export.resize)
+        if any(a.chroma_format == 1 for _, _, a in parsed) and ((int(export.size[0]) | int(export.size[1])) & 1):
+            raise UnsupportedHeif("an alpha auxiliary image coded 4:2:0 cannot be resized to an odd size %d x %d "
+                                  "(monochrome alpha images have no such limit)" % (int(export.size[0]), int(export.size[1])))
     frames, col = _decode_items([(c, info) for c, info, _ in parsed], export, device, verify_hash, hash_on, colour, timing)
     alpha = None
-    if all(a is not None for _, _, a in parsed):
-        alpha, _ = _decode_items([(c, a) for c, _, a in parsed], recon.ExportSpec(format="planar"), device, verify_hash,
-                                 hash_on, "file", timing)
+    if with_alpha:
+        alpha, _ = _decode_items([(c, a) for c, _, a in parsed], alpha_spec, device, verify_hash, hash_on, "file", timing)
+    if export.size is not None:
+        w, h = int(export.size[0]), int(export.size[1])
+        return [HeifImage(frames, alpha, w, h, p[1].bit_depth, p[1].orientation, col, p[1].icc, timing, i, p[1].size)
+                for i, p in enumerate(parsed)]
     info = parsed[0][1]
     w, h = info.size
-    return [HeifImage(frames, alpha, w, h, info.bit_depth, info.orientation, col, p[1].icc, timing, i)
+    return [HeifImage(frames, alpha, w, h, info.bit_depth, info.orientation, col, p[1].icc, timing, i, (w, h))
             for i, p in enumerate(parsed)]

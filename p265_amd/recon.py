@@ -241,6 +241,54 @@ class GridSpec:
         return (h, w) if self.orientation & 1 else (w, h)
 
 
+@dataclass(frozen=True)
+class GridFrame:
+    """A p265r_grid_frame, one frame of the scaled grid export (ReconContext.export_grid_resized): ``rows`` x ``cols``
+    tiles (row-major) form the frame's canvas, of which ``out_width`` x ``out_height`` is the image; ``crop`` = (left,
+    right, top, bottom) cuts the window inside that image; ``orientation`` = k | m << 2 as for GridSpec."""
+    rows: int
+    cols: int
+    out_width: int
+    out_height: int
+    crop: tuple = (0, 0, 0, 0)
+    orientation: int = 0
+
+    def fill(self, f):
+        f.rows, f.cols, f.out_width, f.out_height = int(self.rows), int(self.cols), int(self.out_width), int(self.out_height)
+        f.crop_left, f.crop_right, f.crop_top, f.crop_bottom = (int(v) for v in self.crop)
+        f.orientation = int(self.orientation)
+        return f
+
+    @property
+    def tiles(self):
+        return int(self.rows) * int(self.cols)
+
+
+def grid_frames_c(frames):
+    """The p265r_grid_frame array of a list of GridFrame."""
+    arr = (_lib.GridFrame * max(len(frames), 1))()
+    for i, f in enumerate(frames):
+        f.fill(arr[i])
+    return arr
+
+
+def grid_resize_plan(params, spec, frames, tile=None):
+    """The per-frame constants of the scaled grid export's kernels (p265r_grid_resize_plan, host only): per frame a
+    dict of tile0, cols, window (left, top, W, H), pre_turn (pw, ph), fx, fy, transpose, stage."""
+    d, rs = spec.desc(), spec.resize_desc()
+    pc = _params_c(params)
+    tw, th = (0, 0) if tile is None else (int(tile[0]), int(tile[1]))
+    out = (ctypes.c_int32 * (12 * max(len(frames), 1)))()
+    _lib.check(_lib.load().p265r_grid_resize_plan(ctypes.byref(pc), tw, th, ctypes.byref(d), ctypes.byref(rs),
+                                                  grid_frames_c(frames), len(frames), out), "p265r_grid_resize_plan")
+    res = []
+    for i in range(len(frames)):
+        v = [int(x) for x in out[12 * i:12 * i + 12]]
+        res.append({"tile0": v[0], "cols": v[1], "window": tuple(v[2:6]), "pre_turn": (v[6], v[7]), "fx": v[8], "fy": v[9],
+                    "transpose": v[10], "stage": v[11]})
+    return res
+
+
 def grid_layout(params, spec, grid, tile=None):
     """ExportLayout of the frame a grid of ``tile`` = (width, height) pictures (default: the params' size) gives,
     through the C p265r_grid_layout (host only: no context, no device).  Every plane view has the oriented frame's
@@ -734,6 +782,39 @@ class ReconContext:
                 buf.free()
             raise
         return DeviceFrames(dst, dst_bytes, lay, [lay.size] * n_frames, buffer=buf, ctx=self, batch=batch)
+
+    def export_grid_resized(self, batch, spec, frames, dst=None, dst_bytes=None, only=None):
+        """Enqueue, after the batch's runs, the scaled grid export (p265r_batch_export_grid_resized) and return at once
+        -> DeviceFrames, one slot of ``spec.size`` per GridFrame of ``frames``, whatever its grid, window or
+        orientation: ``batch_array()`` is the dense view.  ``only`` lists the tiles frame after frame (None: the batch
+        in order); ``dst`` / ``dst_bytes`` as for ``export``."""
+        from . import hip
+        if spec.size is None:
+            raise ValueError("export_grid_resized: ExportSpec.size, the (width, height) of every slot")
+        frames = list(frames)
+        idx = list(range(len(batch.pics))) if only is None else [int(i) for i in only]
+        if not frames or sum(f.tiles for f in frames) != len(idx) or any(not 0 <= i < len(batch.pics) for i in idx):
+            raise _lib.P265RError(_lib.EINVAL, "p265r_batch_export_grid_resized")
+        lay = self.export_layout(spec)
+        buf = None
+        if dst is None:
+            hip.set_device(self.device)
+            dst_bytes = lay.frame_bytes * len(frames)
+            buf = hip.DeviceBuffer(dst_bytes)
+            dst = buf.ptr.value
+        elif dst_bytes is None:
+            raise ValueError("dst_bytes: the size of the caller's buffer")
+        arr = (ctypes.c_int32 * len(idx))(*idx) if only is not None else None
+        try:
+            _lib.check(self.lib.p265r_batch_export_grid_resized(self.handle, batch.handle, ctypes.byref(lay.desc),
+                                                                ctypes.byref(lay.resize), grid_frames_c(frames), len(frames),
+                                                                ctypes.c_void_p(int(dst)), int(dst_bytes), arr),
+                       "p265r_batch_export_grid_resized")
+        except BaseException:
+            if buf is not None:
+                buf.free()
+            raise
+        return DeviceFrames(dst, dst_bytes, lay, [lay.size] * len(frames), buffer=buf, ctx=self, batch=batch)
 
     def sync(self):
         _lib.check(self.lib.p265r_sync(self.handle), "p265r_sync")
